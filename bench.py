@@ -2,6 +2,7 @@
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config default|sr|kate|library|snail]
                   [--closure fused|notebook] [--no-graph] [--instances B [--group both|native|graphs]]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one optimisation iteration (reg-noise perturbation, skip-net forward, MSE, backward,
@@ -20,17 +21,29 @@ max-over-ranks time only -- no RCCL anywhere).
 
 Timed region: K iterations with the fused closure (utils.reg_noise.RegNoise +
 utils.loss_head.MSEHead + in-place EMA), executed as eager launches on the engine's two HIP streams
-or as K replays of the iteration captured into a hipGraph (dip_optim.GraphedIteration);
-`--mode auto` (default) times K steps each way and reports the faster as `value`, the other under
-"other_mode".  `--closure notebook --mode eager` times the notebook's own torch closure; the default
-line reports that figure too (`eager_notebook`) from a short extra run.
+or as K replays of the iteration captured into a hipGraph (dip_optim.GraphedIteration).
+A plain run sets up, warms up W steps, times exactly K steps of ONE form, writes `--dump-outputs` and prints
+the JSON line: `--mode auto` (default) then times the form that wins for the configuration (PLAIN_AUTO_MODE:
+eager launches, the hipGraph for snail).  `--full` adds everything the headline does not need: `--mode auto`
+times K steps each way and reports the faster as `value`, the other under "other_mode", and the line
+carries the extra measurements listed below.  `--closure notebook --mode eager` times the notebook's own
+torch closure; the `--full` line reports that figure too (`eager_notebook`) from a short extra run.
+
+`--dump-outputs DIR` writes what the last timed step computed (network output, EMA output, loss, parameters
+after the Adam step) as DIR/<name>.npy in float32, at most 64 MB (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 `--instances B` (> 1): B independent fits per GPU, timed as ONE launch list that serves all of them
 (dip_group.GroupedFits: every kernel launch covers the B instances) and as one hipGraph per
-fit on its own stream; the faster is `value`, the others go to "other_mode".  The default line carries a
-short run of that form as `grouped_batch_of_4` (4 fits of the headline configuration on the GPU).
+fit on its own stream; the faster is `value`, the others go to "other_mode" (a plain run times the grouped
+launch list only).  The `--full` default line carries a short run of that form as `grouped_batch_of_4` (4 fits
+of the headline configuration on the GPU).
 
-The JSON line also carries
+Every JSON line carries
+  build_id       : (round 5) dip_build_id(): the sha256 of the sources the loaded libdip_hip.so was built from;
+  per_rank_final_loss_hex : every rank's final loss, exact; `--gpus 1 --first-image r` is the solo run of rank r's fit
+                   (tests/test_shard_gpu.py compares the two bit for bit).
+The `--full` JSON line also carries
   roofline       : the dominant kernel (3x3 stride-1 implicit-GEMM conv, 128-wide N block: forward
                    and data-gradient launches) -- ALGORITHMIC FLOPs (2*Cout*Hout*Wout*
                    Cin*k*k of the layer, no padded ring, no dilation zeros) / the kernel's own
@@ -40,10 +53,7 @@ The JSON line also carries
   cpu_baseline   : the CPU oracle (oracle/dip_oracle.py, a bitwise-verified restatement of the
                    reference's PyTorch-CPU path) timed on this box's host cores on the same workload;
   sustained      : (round 5) BASELINE.md section 4's own protocol next to the driver's short one -- 50 warm-up + 300 timed
-                   iterations of the reported mode, with the PPT / sclk samples of that region;
-  build_id       : (round 5) dip_build_id(): the sha256 of the sources the loaded libdip_hip.so was built from;
-  per_rank_final_loss_hex : every rank's final loss, exact; `--gpus 1 --first-image r` is the solo run of rank r's fit
-                   (tests/test_shard_gpu.py compares the two bit for bit).
+                   iterations of the reported mode, with the PPT / sclk samples of that region.
 """
 import argparse
 import json
@@ -69,6 +79,10 @@ CONFIGS = {
     "library": dict(size=(448, 704), desc="inpainting 'library' skip-net (depth 6, 5x5 down filters) 448x704, masked MSE"),
     "snail": dict(size=(256, 384), desc="denoising 'snail' skip-net (8..128 channels) 256x384"),
 }
+# `--mode auto` without --full times one form only: the one that wins for the configuration (at 512^2 and
+# above the eager two-stream schedule, for the small snail net the hipGraph).  --full times both and reports the faster.
+PLAIN_AUTO_MODE = {"snail": "graph"}
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 # ------------------------------------------------------------------------------ rank plumbing
@@ -1033,6 +1047,48 @@ def timed_run_grouped(g, steps, warmup, use_graph, barrier):
     return t1 - t0, ps.summary(t0, t1)
 
 
+def dump_outputs(out_dir, fits, grouped, rank, world, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed step gave its caller, per fit -- the network output, the EMA of the outputs
+    (denoising configs), the loss and every parameter after the optimiser step (flattened in named_parameters() order) --
+    as out_dir/<name>.npy in float32.  Per-fit names carry a fit{i}_ prefix when a rank runs several fits and a rank{r}_
+    prefix on multi-GPU runs.  Above `limit` bytes in all, each large array is replaced by a fixed seeded sample of its
+    elements (sorted indices, the same from run to run) so that the total fits."""
+    import torch
+    torch.cuda.synchronize()
+    arrays = {}
+    if grouped is not None:
+        per_fit = [(grouped.out[b], None if grouped.out_avg is None else grouped.out_avg[b], grouped.losses[b], net)
+                   for b, net in enumerate(grouped.nets)]
+    else:
+        per_fit = [(f.engine.last_out, f.avg, f.loss, f.net) for f in fits]
+    for i, (out, avg, loss, net) in enumerate(per_fit):
+        pre = (f"rank{rank}_" if world > 1 else "") + (f"fit{i}_" if len(per_fit) > 1 else "")
+        arrays[pre + "output"] = out
+        if avg is not None:
+            arrays[pre + "output_ema"] = avg
+        arrays[pre + "loss"] = loss.reshape(1)
+        arrays[pre + "params"] = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    budget = limit // max(world, 1) - 256 * len(arrays)       # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        # shrink the largest arrays first: every array keeps min(its size, an equal share of what the smaller ones leave)
+        left, n_left = budget, len(arrays)
+        for k in sorted(arrays, key=lambda k: arrays[k].nbytes):
+            share = left // n_left // 4
+            a = arrays[k].reshape(-1)
+            if a.size > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+                arrays[k + "_sample"] = a[idx]
+                del arrays[k]
+                a = a[idx]
+            left -= a.nbytes
+            n_left -= 1
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def selftest_rank(args, rank, world, barrier):
     """DIP_BENCH_SELFTEST=1: the N-rank plumbing (spawn, rendezvous, barrier, max-over-ranks, per-rank
     gather, JSON) with a dummy CPU step instead of the GPU fit -- driven by tests/test_host.py."""
@@ -1063,11 +1119,23 @@ def main():
     ap.add_argument("--first-image", type=int, default=0,
                     help="index (= seed) of the first image: `--gpus 1 --first-image r` is the solo run of what rank r of a "
                          "multi-GPU run fits (per_rank_final_loss_hex must match bit for bit: tests/test_shard_gpu.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-eager-line", action="store_true")
-    ap.add_argument("--dump-ops", default=None, help="write the per-launch HIP-event table (JSON) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also take what the headline does not need: both modes under --mode auto (and both grouped forms "
+                         "under --group both), rooflines, CPU baseline, notebook-closure / fp32-only / batch-of-4 / sustained "
+                         "runs, host issue time")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (network output, EMA output, loss, "
+                         "parameters) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) leave out the per-launch profile and rooflines")
+    ap.add_argument("--no-eager-line", action="store_true",
+                    help="(--full) leave out the notebook-closure, fp32-only, batch-of-4 and sustained runs")
+    ap.add_argument("--dump-ops", default=None, help="(--full) write the per-launch HIP-event table (JSON) here")
     args = ap.parse_args()
+    if not args.full:                   # a plain run: set up, warm up, time the K steps, dump, print the line
+        args.no_cpu_baseline = args.no_roofline = args.no_eager_line = True
+        if args.dump_ops:
+            raise SystemExit("bench.py: --dump-ops needs --full (the per-launch profile is a run of its own)")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -1104,7 +1172,14 @@ def main():
         return
 
     import __graft_entry__ as ge
-    ge.build()
+    if ge.library_id() == ge.source_id():
+        # built and current: load it as it is -- build() takes a write lock next to the library, and the tree may be
+        # read-only to the user who runs the benchmark
+        ge.add_to_path()
+        import dip_native
+        assert dip_native.lib().dip_abi_version() == dip_native.ABI_VERSION
+    else:
+        ge.build()
     assert torch.cuda.is_available(), "bench.py needs an MI355X"
     if local >= torch.cuda.device_count():
         raise SystemExit(f"bench.py: rank {rank} wants GPU {local} but only {torch.cuda.device_count()} are visible")
@@ -1120,7 +1195,11 @@ def main():
     # `auto` times K steps in each mode and reports the faster one as `value` (the other goes to
     # "other_mode"): at 512x512 the GPU is throughput-bound and the eager two-stream schedule wins, small
     # nets are launch-bound and the graph wins.
-    modes = {"graph": [True], "eager": [False], "auto": [False, True]}["eager" if args.no_graph else args.mode]
+    # A plain run times K steps of ONE form: under `auto` the one that wins for this configuration (PLAIN_AUTO_MODE).
+    mode = "eager" if args.no_graph else args.mode
+    if mode == "auto" and not args.full:
+        mode = PLAIN_AUTO_MODE.get(args.config, "eager")
+    modes = {"graph": [True], "eager": [False], "auto": [False, True]}[mode]
     # per-launch HIP-event timing for the roofline objects: BEFORE any hipGraph exists in the process (event churn
     # after a captured graph had been torn down aborted 10-25 % of the small-config runs on ROCm 7.2 with glibc
     # heap-corruption errors; in this order: 0 / 60)
@@ -1131,13 +1210,16 @@ def main():
         torch.cuda.synchronize()
         per_op = profile_ops(fits[0].engine)
     runs = []
+    last = None                  # the form whose timed steps ran last: what --dump-outputs writes
     native_ok = n_inst > 1 and args.closure == "fused" and args.config != "sr" and args.group != "graphs"
-    if not (native_ok and args.group == "native"):
+    # (a plain run with --group both times the grouped launch list only: the faster form)
+    if not (native_ok and (args.group == "native" or not args.full)):
         for use_graph in modes:
             t, graphed, note, power = timed_run(fits, args.steps, args.warmup, use_graph, barrier)
             runs.append({"t": reduce_max_time(t), "mine": len(fits) * args.steps / t, "graphed": graphed, "note": note,
                          "power": power, "form": "one hipGraph per fit on its own stream" if graphed else
                          "eager launch lists, one fit after the other", "loss": float(fits[0].loss.item())})
+            last = "fits"
     grouped = None
     if native_ok:
         # the same fits through ONE launch list (csrc/dip_group.h): every kernel launch serves all n_inst instances
@@ -1149,8 +1231,10 @@ def main():
                              "power": power, "form": f"grouped: one launch list for the {n_inst} fits"
                              + (", replayed as ONE hipGraph" if use_graph else ", eager launches"),
                              "loss": float(grouped.losses[0].item()), "native_mask": int(grouped.lib.dip_group_native(-1))})
+                last = "grouped"
         except Exception as e:
-            if args.group == "native" or world > 1:      # (all ranks must time the same forms: no silent per-rank divergence)
+            # (all ranks must time the same forms: no silent per-rank divergence; a plain run has no other form)
+            if args.group == "native" or world > 1 or not args.full:
                 raise
             runs.append({"t": float("inf"), "mine": 0.0, "graphed": False, "power": None, "loss": float("nan"),
                          "note": f"grouped form failed: {type(e).__name__}: {e}", "form": "grouped (failed)"})
@@ -1169,8 +1253,10 @@ def main():
     pw = best.get("power") or {}
     per_rank_power = gather_floats(float(pw.get("power_w_mean") or float("nan")))
     per_rank_sclk = gather_floats(float(pw.get("sclk_mhz_mean") or float("nan")))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fits if last == "fits" else None, grouped if last == "grouped" else None, rank, world)
     rank_issue = None
-    if world > 1 and not best["graphed"] and not best["form"].startswith("grouped"):
+    if args.full and world > 1 and not best["graphed"] and not best["form"].startswith("grouped"):
         try:
             rank_issue = host_issue(fits).get("command_list_ms_per_iteration")
         except Exception:
@@ -1251,7 +1337,7 @@ def main():
                          "warmup": 50, "hipgraph": sg, "power": spower,
                          "what": "BASELINE.md section 4 protocol: 50 warm-up + 300 timed iterations, same fit, same mode"}
         hissue = None
-        if world == 1 and n_inst == 1 and not graphed and os.environ.get("DIP_BENCH_CHILD") is None:
+        if args.full and world == 1 and n_inst == 1 and not graphed and os.environ.get("DIP_BENCH_CHILD") is None:
             try:
                 hissue = host_issue(fits)
             except Exception as e:          # the headline does not depend on it

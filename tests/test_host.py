@@ -384,9 +384,11 @@ def test_grouped_iteration_issues_its_launch_list_without_a_gpu(built):
     """The host side of one grouped iteration end to end, without a GPU: every launch of the list goes through the real
     C ABI (argument marshalling, dispatch, the slab range check) and fails at hipLaunchKernel with "no ROCm-capable device"
     (rc 100), which this test -- and only this test -- tolerates; anything else (a bad argument, a refused launch, a Python
-    error) fails it.  In a subprocess: it patches torch.cuda's stream accessors."""
+    error) fails it.  In a subprocess: it patches torch.cuda's stream accessors.  The launches carry HOST pointers, so the
+    subprocess hides every GPU (HIP_VISIBLE_DEVICES=-1) and stops before the first launch if one is still visible."""
     code = r"""
 import sys, contextlib, torch
+assert torch.cuda.device_count() == 0, "a GPU is visible: the walk launches with host pointers and must not reach one"
 sys.path.insert(0, %r)
 import dip_native as N
 from models.skip import skip
@@ -424,7 +426,8 @@ assert g._nbt_all.unique().tolist() == [2]
 print("WALK_OK", len(failed))
 """ % os.path.join(ROOT, "deep-image-prior_amd")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, DIP_TWO_STREAMS="0", DIP_NO_CLIST="1"))      # (launch by launch: a command list stops at its first failure)
+                       env=dict(os.environ, DIP_TWO_STREAMS="0", DIP_NO_CLIST="1",      # (launch by launch: a command list stops at its first failure)
+                                HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1"))
     assert "WALK_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 

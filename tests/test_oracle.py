@@ -1,16 +1,14 @@
 """CPU suite: the oracle (oracle/dip_oracle.py) against the committed golden vectors that the REAL
-reference produced (oracle/make_golden.py), plus -- when the reference checkout is present (build
-container only) -- the bitwise check against the reference itself."""
+reference produced (oracle/make_golden.py), plus the bitwise check against the reference itself through the digests
+of its tensors (oracle/reference_pin.py)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 import dip_oracle as O
 from test_net_gpu import NETS
 
@@ -99,12 +97,24 @@ def test_oracle_default_net_digest():
     assert abs(loss.item() - dg["loss"]) <= 1e-6 * dg["loss"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference checkout not mounted")
 def test_oracle_bitwise_equal_to_reference():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "verify_against_reference.py")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "oracle pinned against the reference" in r.stdout
+    """The ten net configurations of oracle/verify_against_reference.py (output, loss, every gradient, every parameter
+    after one Adam step), the Downsampler and get_noise: the oracle's tensors against the SHA-256 digests of the real
+    reference's on the same inputs (tests/golden/reference_pin.json, oracle/reference_pin.py) -- bitwise equality."""
+    import reference_pin
+    gold = json.load(open(os.path.join(GOLDEN, "reference_pin.json")))
+    torch.set_num_threads(1)
+    try:
+        got = reference_pin.oracle_digests()
+    finally:
+        torch.set_num_threads(min(16, os.cpu_count() or 1))
+    for name, g in gold["nets"].items():
+        o = got["nets"][name]
+        assert o["out"] == g["out"] and o["loss"] == g["loss"], (name, o["loss"], g["loss"])
+        assert o["grad"] == g["grad"], (name, sorted(k for k in g["grad"] if o["grad"].get(k) != g["grad"][k]))
+        assert o["adam1"] == g["adam1"], (name, sorted(k for k in g["adam1"] if o["adam1"].get(k) != g["adam1"][k]))
+    assert set(got["nets"]) == set(gold["nets"])
+    assert got["downsampler"] == gold["downsampler"] and got["get_noise"] == gold["get_noise"]
 
 
 def test_closure_bookkeeping_restates_the_notebook_rule():

@@ -13,4 +13,4 @@ B="--steps 10 --warmup 3 --mode eager --no-cpu-baseline --no-roofline --no-eager
 ( cd /tmp && timeout 120 rocprofv3 --kernel-trace --stats -d $OLDPWD/$O/prof1 -o trace -- env DIP_TWO_STREAMS=0 python $OLDPWD/bench.py $B > $OLDPWD/$O/prof1.log 2>&1 )
 python tools/prof_summary.py $O/prof1 13 > $O/kernel_stats_single_stream.txt 2>> $O/prof1.log
 rm -rf $O/prof1; stamp "prof done"
-timeout 200 python bench.py --steps 100 --warmup 10 > $O/bench.log 2>&1; grep '^{"metric"' $O/bench.log | tail -1 > $O/bench_line.json; stamp "bench done"
+timeout 200 python bench.py --full --steps 100 --warmup 10 > $O/bench.log 2>&1; grep '^{"metric"' $O/bench.log | tail -1 > $O/bench_line.json; stamp "bench done"

@@ -11,6 +11,6 @@ B="--steps 10 --warmup 3 --mode eager --no-cpu-baseline --no-roofline --no-eager
 ( cd /tmp && env DIP_TWO_STREAMS=0 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof1 -o trace -- python $ROOTD/bench.py $B > $O/prof_bench.log 2>&1 )
 python tools/prof_summary.py $O/prof1 13 2>> $O/err.log | cut -c1-170 | head -12 | tee $O/stats.txt
 rm -rf $O/prof1
-python bench.py --steps 100 --warmup 10 --mode eager --no-cpu-baseline --no-eager-line --dump-ops $O/ops.json 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["largest_layer"])'
+python bench.py --full --steps 100 --warmup 10 --mode eager --no-cpu-baseline --no-eager-line --dump-ops $O/ops.json 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["largest_layer"])'
 rm -f gpurun_out/ab.log
 REPS=2 STEPS=150 tools/gpu_ab.sh

@@ -30,15 +30,15 @@ TMO=900 run python -m pytest tests/test_kernels_gpu.py -q -m gpu --no-header -p 
 fi
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  TMO=900 run python bench.py --steps 100 --warmup 10 --dump-ops gpurun_out/ops.json
+  TMO=900 run python bench.py --full --steps 100 --warmup 10 --dump-ops $(dirname $LOG)/ops.json
   grep '^{"metric"' $LOG | tail -1 > gpurun_out/bench.json
   for cfg in ${EXTRA_BENCH:-}; do
-    TMO=600 run python bench.py --config $cfg --steps 60 --warmup 10 --no-cpu-baseline --dump-ops gpurun_out/ops_$cfg.json
+    TMO=600 run python bench.py --full --config $cfg --steps 60 --warmup 10 --no-cpu-baseline --dump-ops $(dirname $LOG)/ops_$cfg.json
     grep '^{"metric"' $LOG | tail -1 > gpurun_out/bench_$cfg.json
   done
   if [ -n "${BENCH_INSTANCES:-}" ]; then
     for cfg in snail library; do
-      TMO=600 run env DIP_TWO_STREAMS=0 python bench.py --config $cfg --instances $BENCH_INSTANCES --steps 60 --warmup 10 --no-cpu-baseline --no-roofline --no-eager-line
+      TMO=600 run env DIP_TWO_STREAMS=0 python bench.py --full --config $cfg --instances $BENCH_INSTANCES --steps 60 --warmup 10 --no-cpu-baseline --no-roofline --no-eager-line
       grep '^{"metric"' $LOG | tail -1 > gpurun_out/bench_${cfg}_x$BENCH_INSTANCES.json
     done
   fi

@@ -30,14 +30,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   TMO=600 run python __graft_entry__.py smoke
   TMO=3000 run python -m pytest tests -q -m gpu --no-header -p no:cacheprovider
 fi
-TMO=900 run python bench.py --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
+TMO=900 run python bench.py --full --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
 grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_line.json
 for cfg in sr kate library snail; do
-  TMO=600 run python bench.py --config $cfg --steps 60 --warmup 10 --no-cpu-baseline
+  TMO=600 run python bench.py --full --config $cfg --steps 60 --warmup 10 --no-cpu-baseline
   grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_$cfg.json
 done
 for cfg in snail library; do
-  TMO=600 run env DIP_TWO_STREAMS=0 python bench.py --config $cfg --instances 8 --steps 60 --warmup 10 --no-cpu-baseline --no-roofline --no-eager-line
+  TMO=600 run env DIP_TWO_STREAMS=0 python bench.py --full --config $cfg --instances 8 --steps 60 --warmup 10 --no-cpu-baseline --no-roofline --no-eager-line
   grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_${cfg}_x8.json
 done
 B="--steps 10 --warmup 3 --mode eager --no-cpu-baseline --no-roofline --no-eager-line"

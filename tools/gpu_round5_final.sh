@@ -21,7 +21,7 @@ python tools/pmc_summary.py $O/pmc_WRITE_SIZE > $O/${T}_rocprofv3_pmc_WRITE_SIZE
 ( cd /tmp && TMO=100 run rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_MFMA -o pmc -- $PRE python $ROOTD/bench.py $P )
 python tools/pmc_mfma.py $O/pmc_cal $O/pmc_MFMA $O/${T}_pmc_mfma.json > $O/${T}_rocprofv3_pmc_MFMA.txt 2>> $LOG
 cp $O/${T}_pmc_traffic.json $O/${T}_pmc_mfma.json profiles/ 2>> $LOG       # (bench.py reads them: same call, same box)
-TMO=200 run python bench.py --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
+TMO=200 run python bench.py --full --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
 grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_line.json
 B="--steps 10 --warmup 3 --mode eager --no-cpu-baseline --no-roofline --no-eager-line"
 ( cd /tmp && TMO=100 run rocprofv3 --kernel-trace --stats -d $O/prof1 -o trace -- env DIP_TWO_STREAMS=0 python $ROOTD/bench.py $B )

@@ -23,7 +23,7 @@ python tools/pmc_summary.py $O/pmc_WRITE_SIZE > $O/${T}_rocprofv3_pmc_WRITE_SIZE
 python tools/pmc_mfma.py $O/pmc_cal $O/pmc_MFMA $O/${T}_pmc_mfma.json > $O/${T}_rocprofv3_pmc_MFMA.txt 2>> $LOG
 TMO=120 run python tools/ubench_ceilings.py $O/${T}_ubench_ceilings.json
 cp $O/${T}_pmc_traffic.json $O/${T}_pmc_mfma.json $O/${T}_ubench_ceilings.json profiles/ 2>> $LOG       # (bench.py reads them: same call, same box)
-TMO=400 run env DIP_BENCH_PMC_SAME_CALL=1 python bench.py --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
+TMO=400 run env DIP_BENCH_PMC_SAME_CALL=1 python bench.py --full --steps 100 --warmup 10 --dump-ops $O/${T}_ops.json
 grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_line.json
 B="--steps 10 --warmup 3 --mode eager --no-cpu-baseline --no-roofline --no-eager-line"
 ( cd /tmp && TMO=100 run rocprofv3 --kernel-trace --stats -d $O/prof1 -o trace -- env DIP_TWO_STREAMS=0 python $ROOTD/bench.py $B )
@@ -38,11 +38,11 @@ python tools/prof_summary.py $O/prof3 13 > $O/${T}_rocprofv3_kernel_stats_librar
 python tools/prof_timeline.py $O/prof3 3 > $O/${T}_timeline_library.txt 2>> $LOG
 rm -rf $O/prof1 $O/prof2 $O/prof3 $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_cal $O/pmc_MFMA
 for cfg in library kate sr snail; do
-  TMO=300 run python bench.py --config $cfg --steps 100 --warmup 10 --no-cpu-baseline --dump-ops $O/${T}_ops_$cfg.json
+  TMO=300 run python bench.py --full --config $cfg --steps 100 --warmup 10 --no-cpu-baseline --dump-ops $O/${T}_ops_$cfg.json
   grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_$cfg.json
 done
 for cfg in library snail; do
-  TMO=300 run python bench.py --config $cfg --instances 8 --steps 50 --warmup 5 --no-cpu-baseline --no-roofline --no-eager-line
+  TMO=300 run python bench.py --full --config $cfg --instances 8 --steps 50 --warmup 5 --no-cpu-baseline --no-roofline --no-eager-line
   grep '^{"metric"' $LOG | tail -1 > $O/${T}_bench_${cfg}_x8.json
 done
 TMO=200 run python __graft_entry__.py smoke
