@@ -224,8 +224,13 @@ __global__ __launch_bounds__(256) void conv_thin4_mfma_kernel(const DipConvDesc 
         // order gives: the loads of rows hr + 1 and hr + 2 are the only vector-memory loads younger than row hr's) 3 % of the
         // backward passes of a 256 x 256 net came out with wrong thin columns WHEN a chip-filling wgrad_bf3 launch ran beside
         // this kernel (DIP_DEFER_WGRAD=-1; tools/race_loop.py: 48 of 1500 passes, differences 1e-7 .. garbage), none without
-        // one (3000 of 3000 bit-identical), none with vmcnt(0) (2000) and none with this form (4000).  Not explained -- the ISA
-        // shows the expected order and tools/isa_inflight_check.py finds nothing -- so the margin is kept; it costs nothing measurable (53 us at 512^2, 28 us per launch on average, as before).
+        // one (3000 of 3000 bit-identical), none with vmcnt(0) (2000) and none with this form (4000).  A candidate cause, from
+        // the control-flow walk of tools/isa_inflight_check.py on the earlier loop (second and third row inside `if`s; its
+        // machine code was the same for both counts but for the wait immediates): hipcc peeled the first iteration and, on
+        // entering the loop, copied row 3's registers (loaded into a0 in the peeled iteration) into the loop's a0 registers
+        // (v_mov_b64 at NJ = 8).  With vmcnt(2 NJ) row 3 is still in flight at that copy, so a late row 3 leaves stale values
+        // in the copy; with vmcnt(NJ) row 2's wait has retired it.  The margin is kept; it costs nothing
+        // measurable (53 us at 512^2, 28 us per launch on average, as before).
         asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a[0]) : "n"(NJ));
 #pragma unroll
         for (int j = 1; j < NJ; ++j) asm volatile("" : "+v"(a[j]));
@@ -239,8 +244,7 @@ __global__ __launch_bounds__(256) void conv_thin4_mfma_kernel(const DipConvDesc 
     const bool owrite = pxo < T4M_SW && ox < d.Wout && no < ncols;
     const int pitch = d.y_pitch > 0 ? d.y_pitch : d.Wout;
     const float bias = (d.bias != nullptr && no < ncols) ? d.bias[no] : 0.f;
-    auto row = [&](int hr, f32x4 (&a)[NJ], bool ok) {
-        waitA(a, ok);
+    auto row = [&](int hr, f32x4 (&a)[NJ]) {                        // (after waitA)
         f32x4 acc[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -284,17 +288,20 @@ __global__ __launch_bounds__(256) void conv_thin4_mfma_kernel(const DipConvDesc 
     bool ok0, ok1, ok2;
     loadA(0, a0, ok0);
     loadA(1, a1, ok1);
+    // The loads and waits are the same on every path through the loop body; only the arithmetic of rows past the walk is
+    // skipped.  (With the second and third load / wait inside the `if`s, a path that skips them and takes the back edge
+    // re-enters the header with a row's load in flight while hipcc reuses its registers -- a path no wave takes, since
+    // the walk ends there, but one that tools/isa_inflight_check.py, which follows every path, cannot rule out.)
     for (int hr = 0; hr < nhr; hr += 3) {
         loadA(hr + 2, a2, ok2);
-        row(hr, a0, ok0);
-        if (hr + 1 < nhr) {
-            loadA(hr + 3, a0, ok0);
-            row(hr + 1, a1, ok1);
-        }
-        if (hr + 2 < nhr) {
-            loadA(hr + 4, a1, ok1);
-            row(hr + 2, a2, ok2);
-        }
+        waitA(a0, ok0);
+        row(hr, a0);
+        loadA(hr + 3, a0, ok0);
+        waitA(a1, ok1);
+        if (hr + 1 < nhr) row(hr + 1, a1);
+        loadA(hr + 4, a1, ok1);
+        waitA(a2, ok2);
+        if (hr + 2 < nhr) row(hr + 2, a2);
     }
     asm volatile("s_waitcnt vmcnt(0)");                               // (the rows loaded past the walk)
 }

@@ -16,8 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("switches", [{}, {"DIP_DEFER_WGRAD": "-1"}, {"DIP_DEFER_WGRAD": "0", "DIP_TAIL_INLINE": "0"},
-                                      {"RACE_NET": "deep"}, {"RACE_NET": "deep", "DIP_DEFER_WGRAD": "-1"}],
-                         ids=["default", "no_deferral", "defer0", "five_scales", "five_scales_no_deferral"])
+                                      {"RACE_NET": "deep"}, {"RACE_NET": "deep", "DIP_DEFER_WGRAD": "-1"},
+                                      {"RACE_NET": "narrow"}, {"RACE_NET": "narrow", "DIP_DEFER_WGRAD": "-1"},
+                                      {"RACE_GROUP": "2"}, {"RACE_GROUP": "2", "DIP_DEFER_WGRAD": "-1"}],
+                         ids=["default", "no_deferral", "defer0", "five_scales", "five_scales_no_deferral", "narrow",
+                              "narrow_no_deferral", "grouped2", "grouped2_no_deferral"])
 def test_backward_passes_are_bit_identical(dev, switches):
     env = {k: v for k, v in os.environ.items() if not k.startswith(("DIP_", "RACE_"))}
     env.update(switches)

@@ -1,6 +1,6 @@
 """Determinism stress for a launch schedule: the switch probe's net (256x256, two scales, 128 channels), fused loss head, N
 backward passes in ONE process, every gradient compared bit for bit with the first pass.  A cross-stream race shows as a
-mismatch.    [DIP_DEFER_WGRAD=-1 ...] python tools/race_loop.py [N]"""
+mismatch.    [DIP_DEFER_WGRAD=-1 RACE_NET=deep|narrow RACE_GROUP=B ...] python tools/race_loop.py [N]"""
 import os
 import sys
 
@@ -20,7 +20,10 @@ def main():
     dev = torch.device("cuda:0")
     hw = (int(os.environ.get("RACE_HW", "256")),) * 2          # RACE_HW=512 RACE_NET=deep: the headline net
     nsc = 5 if os.environ.get("RACE_NET") == "deep" else 2       # deep: the default net's five scales (conv_small, bn_bwd_one, ...)
-    kw = dict(num_channels_down=[128] * nsc, num_channels_up=[128] * nsc, num_channels_skip=[4] * nsc,
+    chans = [128] * nsc
+    if os.environ.get("RACE_NET") == "narrow":                   # conv_thin4 at NJ = 1, 2, 4, 8; conv_thin / wgrad_thin / conv_small
+        chans = [16, 32, 64, 128]
+    kw = dict(num_channels_down=chans, num_channels_up=chans, num_channels_skip=[4] * len(chans),
               upsample_mode="bilinear", need_sigmoid=True, need_bias=True, pad="reflection")
     torch.manual_seed(5)
     z = (torch.rand(1, 4, *hw) * 0.1).to(dev)
@@ -28,6 +31,9 @@ def main():
     mask = (torch.rand(1, 1, *hw) > 0.3).float().to(dev)
     torch.manual_seed(6)
     net = skip(4, 3, **kw).to(dev)
+    group = int(os.environ.get("RACE_GROUP", "0"))
+    if group:
+        return grouped(n, group, net, skip, kw, z, target, mask, dev)
     head = MSEHead(net, target, mask=mask)
     plain = os.environ.get("RACE_PLAIN") == "1"
     ref, bad = None, 0
@@ -59,6 +65,43 @@ def main():
             print(f"pass {it} ({key}): {len(diff)} tensors differ, e.g. {worst}: max|d| "
                   f"{float((cur[worst].double() - ref[key][worst].double()).abs().max()):.3e}", flush=True)
     print(f"{n} passes, {bad} with a mismatch", {k: v for k, v in os.environ.items() if k.startswith('DIP_')})
+
+
+def grouped(n, B, net0, skip, kw, z, target, mask, dev):
+    """RACE_GROUP=B: B fits through dip_group.GroupedFits (one launch list, the native GRP = true kernels on), lr = 0 and no
+    reg-noise so every iteration computes the same gradients; each instance's gradient arena is compared bit for bit with its
+    first pass."""
+    import dip_native
+    from dip_group import GroupedFits
+    lib = dip_native.lib()
+    prev = lib.dip_group_native(0x7fffffff)
+    nets, zs, ts, ms = [net0], [z], [target], [mask]
+    for b in range(1, B):
+        torch.manual_seed(6 + b)
+        nets.append(skip(4, 3, **kw).to(dev))
+        zs.append((torch.rand_like(z) * 0.1).contiguous())
+        ts.append(torch.rand_like(target))
+        ms.append((torch.rand_like(mask) > 0.3).float())
+    g = GroupedFits(nets, zs, ts, masks=ms, reg_noise_std=0.0, seeds=list(range(B)), lr=0.0)
+    ref, bad = None, 0
+    try:
+        for it in range(n):
+            g.step(1)
+            torch.cuda.synchronize()
+            cur = [g._inst(g.eng.grads, b).clone() for b in range(B)]
+            if ref is None:
+                ref = cur
+                assert all(float(c.nan_to_num().abs().sum()) > 0 for c in cur), "degenerate gradients"
+                continue
+            diff = [b for b in range(B) if not (torch.equal(cur[b].isnan(), ref[b].isnan())
+                                                and torch.equal(cur[b].nan_to_num(), ref[b].nan_to_num()))]
+            if diff:
+                bad += 1
+                print(f"pass {it}: instances {diff} differ, max|d| "
+                      f"{max(float((cur[b].double() - ref[b].double()).abs().max()) for b in diff):.3e}", flush=True)
+    finally:
+        lib.dip_group_native(prev)
+    print(f"{n} passes, {bad} with a mismatch", {k: v for k, v in os.environ.items() if k.startswith(("DIP_", "RACE_"))})
 
 
 if __name__ == "__main__":
