@@ -102,13 +102,22 @@ class ScalePlan:
 
 
 class SkipEngine:
+    kind = "skip"                      # which backbone the launch lists serve ("resnet": ResNetEngine)
+
     def __init__(self, net, scales: List[ScalePlan], out_conv: torch.nn.Conv2d, need_sigmoid: bool, pad: str,
                  act_slope: float = 0.2):
+        self._init_common(net, need_sigmoid, pad, act_slope)
+        self._collect_records(scales, out_conv)
+        # the two convs reading net_input need no data gradient unless the input is optimised
+        self.param_list = list(net.parameters())
+        self._check_supported()
+
+    def _init_common(self, net, need_sigmoid: bool, pad: str, act_slope: float):
+        """Options, schedules and switches shared by every backbone's engine."""
         self.net = net
         self.need_sigmoid = need_sigmoid
         self.pad_mode = N.PAD_REFLECT if pad == "reflection" else N.PAD_ZERO
         self.slope = act_slope
-        self.nscales = len(scales)
         self.fwd_id = 0
         self._aux = {}                 # (capture | eager, device) -> ([side stream, bulk stream], events)
         self.two_streams = os.environ.get("DIP_TWO_STREAMS", "1") != "0"
@@ -186,7 +195,9 @@ class SkipEngine:
         # (grouped multi-instance execution, csrc/dip_group.h)
         self.slab = None
 
-        # records in a fixed traversal order
+    def _collect_records(self, scales: List[ScalePlan], out_conv: torch.nn.Conv2d):
+        """Conv / BatchNorm records in a fixed traversal order."""
+        self.nscales = len(scales)
         self.convs: List[ConvRec] = []
         self.bns: List[BNRec] = []
         self.sc = []
@@ -212,9 +223,6 @@ class SkipEngine:
             self.sc.append(rec)
         self.out_conv = ConvRec(out_conv, self.pad_mode, "out")
         self.convs.append(self.out_conv)
-        # the two convs reading net_input need no data gradient unless the input is optimised
-        self.param_list = list(net.parameters())
-        self._check_supported()
 
     # ------------------------------------------------------------------ support matrix
     def _check_supported(self):
@@ -380,30 +388,7 @@ class SkipEngine:
         # The plan is generated twice: a sizing pass (no allocations, no descriptors) that only
         # measures the shared scratch buffers, then the emitting pass.
         for sizing in (True, False):
-            self._sizing = sizing
-            self.fwd_ops, self.bwd_ops, self.bwd_input_ops, self.keep = [], [], [], []
-            if not sizing:
-                self.stats_scratch = self._new(self.stat_need)
-                self.bwd_scratch = self._new(self.bwdp_need)
-                self.wg_scratch = self._new(self.wg_need)
-                self.wgb_scratch = self._new(self.wgb_need)
-                self.wg_scratch2 = self._new(self.wg2_need)
-                self.wgb_scratch2 = self._new(self.wgb2_need)
-                self.ws_scratch = self._new(self.ws_need)
-                self.stats_scratch2 = self._new(self.stat2_need)
-                self.ws_scratch2 = self._new(self.ws2_need)
-                self.bwd_scratch2 = self._new(self.bwdp2_need)
-                self.bwd_scratch3 = self._new(self.bwdp3_need)
-                # zero-initialised; every launch leaves its counters at zero
-                self.tickets = self._dalloc(self.ticket_need, torch.int32, zero=True)
-                self._alloc.append(self.tickets)
-            self._ticket_off = 0
-            self._fused_bnb = {}
-            self._deferred = []
-            self._replicate_bufs = set()
-            self._fwd_side = set()
-            self._bulk2, self._bulk_flip = set(), False
-            self._entered_defer_scale = False
+            self._begin_pass(sizing)
             self.x_nhwc = self._buf(H * W * round_up(Cin_img, 4))
             xin = Act(self.x_nhwc, H, W, Cin_img)
             last = self._plan_scale(0, xin, H, W)
@@ -429,6 +414,34 @@ class SkipEngine:
             self.bwd_ops = pre + self._bwd_scale_ops(0, dy_last)
             self.bwd_ops += self._flush_deferred_wgrads()       # (fewer scales than defer_scale)
         self.shape_key = (H, W, Cin_img)
+
+    def _begin_pass(self, sizing: bool):
+        """Start of one planner pass: empty launch lists; the emitting pass allocates the shared scratch buffers that the
+        sizing pass measured."""
+        self._sizing = sizing
+        self.fwd_ops, self.bwd_ops, self.bwd_input_ops, self.keep = [], [], [], []
+        if not sizing:
+            self.stats_scratch = self._new(self.stat_need)
+            self.bwd_scratch = self._new(self.bwdp_need)
+            self.wg_scratch = self._new(self.wg_need)
+            self.wgb_scratch = self._new(self.wgb_need)
+            self.wg_scratch2 = self._new(self.wg2_need)
+            self.wgb_scratch2 = self._new(self.wgb2_need)
+            self.ws_scratch = self._new(self.ws_need)
+            self.stats_scratch2 = self._new(self.stat2_need)
+            self.ws_scratch2 = self._new(self.ws2_need)
+            self.bwd_scratch2 = self._new(self.bwdp2_need)
+            self.bwd_scratch3 = self._new(self.bwdp3_need)
+            # zero-initialised; every launch leaves its counters at zero
+            self.tickets = self._dalloc(self.ticket_need, torch.int32, zero=True)
+            self._alloc.append(self.tickets)
+        self._ticket_off = 0
+        self._fused_bnb = {}
+        self._deferred = []
+        self._replicate_bufs = set()
+        self._fwd_side = set()
+        self._bulk2, self._bulk_flip = set(), False
+        self._entered_defer_scale = False
 
     def _plan_scale(self, i, xin: Act, H, W):
         s = self.sc[i]
@@ -1215,6 +1228,13 @@ class SkipEngine:
         else:
             self._run(self.bwd_ops, main, "bwd1")
 
+    def _net_cin(self) -> int:
+        return self.sc[0].down_a.Cin
+
+    def _input_gin(self):
+        """Gradient source (buf, pad) wrt the net's input, left by self.bwd_input_ops."""
+        return self.sc[0].gin
+
     def forward(self, x: torch.Tensor, head=None):
         """Runs the forward launch list.  head = None: returns the network output [1,C,H,W].
         head = a utils.loss_head.MSEHead: the output conv + sigmoid + (mask) + MSE run as ONE launch
@@ -1230,8 +1250,8 @@ class SkipEngine:
             self._build_arenas(dev)
         _, Cimg, H, W = x.shape
         if self.shape_key != (H, W, Cimg):
-            if Cimg != self.sc[0].down_a.Cin:
-                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {self.sc[0].down_a.Cin}")
+            if Cimg != self._net_cin():
+                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {self._net_cin()}")
             self._build_plan(H, W, Cimg)
         lib = self.lib
         with torch.cuda.device(dev):          # raw HIP launches go to the CURRENT device's streams
@@ -1311,7 +1331,7 @@ class SkipEngine:
             gx = None
             if need_input_grad:
                 self._run(self.bwd_input_ops, main, "bwdin")
-                gbuf, pad = self.sc[0].gin
+                gbuf, pad = self._input_gin()
                 src = N.DipGradSrc(_ptr(gbuf), pad, 1 if pad > 0 else 0, round_up(self.Cimg, 4), 0)
                 gx = torch.empty((1, self.Cimg, H, W), dtype=torch.float32, device=dev)
                 N.check(lib.dip_fold_to_nchw(C.byref(src), H, W, self.Cimg, gx.data_ptr(), stream), "fold_to_nchw")
@@ -1319,6 +1339,208 @@ class SkipEngine:
         # them in place (keep a .clone() if a gradient has to survive the next closure evaluation)
         views = [grads[o:o + p.numel()].view(p.shape) for p, o in zip(self.param_list, self.slots)]
         return gx, views
+
+
+class TableAct(Act):
+    """An activation WITHOUT a BatchNorm in front of it (the ResNet's first conv, models/resnet.py:60-61 of the reference),
+    as a consumer sees it.  DipTransform.a == NULL means identity to every loader, so the consumers get a ones / zeros
+    coefficient pair (an engine-owned table [2][Cs]) with the activation's slope code."""
+
+    def __init__(self, buf, H, W, Cch, table, slope):
+        super().__init__(buf, H, W, Cch, None, slope)
+        self.table = table
+
+    def transform(self, shape_only=False) -> N.DipTransform:
+        if self.slope == 1.0:           # act_fun='none'
+            return N.DipTransform(None, None, 1.0)
+        if shape_only:
+            return N.DipTransform(1, 1, self.slope)
+        return N.DipTransform(_ptr(self.table), _ptr(self.table, self.Cs), self.slope)
+
+
+class ResBlockRec:
+    """One residual block (get_block, models/resnet.py:33-41 of the reference): conv1 -> bn1 -> act -> conv2 -> bn2."""
+
+    def __init__(self, conv1, bn1, conv2, bn2):
+        self.conv1, self.bn1, self.conv2, self.bn2 = conv1, bn1, conv2, bn2
+        self.st = None
+
+
+class ResNetEngine(SkipEngine):
+    """Launch-list plan of models.resnet.ResNet: a chain at full resolution,
+        x -> conv0 (+bias) -> act -> [ R + bn2(conv2(act(bn1(conv1(R))))) ] x num_blocks -> conv_t (+bias) -> bn_t -> conv_out
+          -> sigmoid
+    built from the emitters of SkipEngine (convolutions with the producer's BatchNorm + activation in their loaders and the
+    consumer's statistics in their epilogues, weight / data gradients, BatchNorm backward) plus the two join launches of
+    csrc/res_kernels.hip.  Per block the forward is conv1, bn_fin, conv2, bn_fin, res_join_fwd; the backward is the BatchNorm
+    backward of bn2 (du = G_{k+1}, no activation), weight + data gradient of conv2, BatchNorm + activation backward of bn1,
+    weight + data gradient of conv1 and res_join_bwd (G_k = G_{k+1} + data gradient; the bottom one also multiplies by the
+    derivative of the first activation and so writes dy of conv0).  The data gradients stay plain stores -- an accumulating
+    descriptor would take them off conv_thin (dip_conv_thin_eligible) -- and the join is a launch of its own.
+    Schedule: every weight gradient is issued where its dy appears (bulk stream), nothing is deferred: the chain has no
+    low-resolution walk to hide them under."""
+    kind = "resnet"
+
+    def __init__(self, net, first_conv, blocks, tail_conv, tail_bn, out_conv, need_residual: bool, pad: str,
+                 act_slope: float = 0.2):
+        # (the reference's constructor appends nn.Sigmoid() whatever need_sigmoid says: models/resnet.py:86-89)
+        self._init_common(net, True, pad, act_slope)
+        self.defer_scale = -1
+        self.nscales, self.sc = 0, []
+        self.need_residual = bool(need_residual)
+        self.first = ConvRec(first_conv, self.pad_mode, "first")
+        self.blocks = []
+        self.bns = []
+        for k, (c1, b1, c2, b2) in enumerate(blocks):
+            # the block convs are nn.Conv2d(C, C, 3, 1, 1): zero padding whatever `pad` says
+            blk = ResBlockRec(ConvRec(c1, N.PAD_ZERO, f"b{k}.conv1"), BNRec(b1, f"b{k}.bn1"),
+                              ConvRec(c2, N.PAD_ZERO, f"b{k}.conv2"), BNRec(b2, f"b{k}.bn2"))
+            self.blocks.append(blk)
+            self.bns += [blk.bn1, blk.bn2]
+        self.tail = ConvRec(tail_conv, N.PAD_ZERO, "tail")
+        self.tail_bn = BNRec(tail_bn, "tail_bn")
+        self.bns.append(self.tail_bn)
+        self.out_conv = ConvRec(out_conv, self.pad_mode, "out")
+        self.convs = [self.first] + [c for b in self.blocks for c in (b.conv1, b.conv2)] + [self.tail, self.out_conv]
+        self.param_list = list(net.parameters())
+        self.gin = None
+        self._check_supported()
+
+    def _check_supported(self):
+        super()._check_supported()
+        if self.first.Cout % 4:
+            raise NotImplementedError("dip-amd: internal channel counts must be multiples of 4")
+        for r in self.convs:
+            if r.ks != 3 or r.stride != 1:
+                raise NotImplementedError(f"dip-amd: ResNet conv {r.name}: only 3x3 stride-1 convs are planned")
+            if r is not self.first and r is not self.out_conv and tuple(r.module.padding) != (1, 1):
+                raise NotImplementedError(f"dip-amd: ResNet conv {r.name}: padding {r.module.padding} (the join needs equal sizes)")
+
+    def _net_cin(self) -> int:
+        return self.first.Cin
+
+    def _input_gin(self):
+        return self.gin
+
+    # ------------------------------------------------------------------ join emitters
+    def _emit_join_fwd(self, xa: Act, xb: Act, out, name):
+        if self._sizing:
+            return
+        ta, tb = xa.transform(), xb.transform()
+        self.keep += [ta, tb]
+        self.fwd_ops.append((self.lib.dip_res_join_fwd, (_ptr(xa.buf), xa.Cs, C.byref(ta), _ptr(xb.buf), xb.Cs, C.byref(tb),
+                                                         _ptr(out), xa.Cs, xa.H * xa.W, xa.C), "res_join_fwd:" + name))
+
+    def _emit_join_bwd(self, g, gd, a: Act, ops, name, act_of: Optional[Act] = None):
+        """(buf, 0) of g + gd [* act'(act_of)]: g = (buf, 0) gradient wrt the block's output or None, gd = the gradient
+        source left by the data gradient of the block's first conv."""
+        if self._sizing:
+            return (None, 0)
+        out = self._new(a.H * a.W * a.Cs)
+        src = self._gradsrc(gd, a.Cs)
+        ty = None
+        if act_of is not None:
+            ty = act_of.transform()
+            self.keep.append(ty)
+        assert g is None or g[1] == 0
+        ops.append((self.lib.dip_res_join_bwd, (_ptr(g[0]) if g is not None else None, a.Cs, C.byref(src),
+                                                _ptr(act_of.buf) if act_of is not None else None, a.Cs,
+                                                C.byref(ty) if ty is not None else None, _ptr(out), a.Cs, a.H, a.W, a.C), name))
+        return (out, 0)
+
+    # ------------------------------------------------------------------ per-shape plan
+    def _build_plan(self, H, W, Cin_img):
+        if min(H, W) < 2:
+            raise NotImplementedError(f"dip-amd: input {H}x{W} is too small for a padded 3x3 convolution")
+        self.H, self.W, self.Cimg = H, W, Cin_img
+        self._clists = {}
+        self._reset_sizing()
+        self._alloc = []
+        oc = self.out_conv
+        self.n_out = oc.Cout
+        if getattr(self, "_bulk2_auto", self.bulk2_max_pixels < 0):
+            # SkipEngine's rule applied to this net's layers: a second bulk stream iff no conv is a big MFMA-bound layer
+            self._bulk2_auto = True
+            big = any(r.Cin >= 96 and r.Cout >= 96 and H * W >= 65536 for r in self.convs)
+            self.bulk2_max_pixels = 0 if big else 100000
+        Cc = self.first.Cout
+        n = H * W * round_up(Cc, 4)
+        for sizing in (True, False):
+            self._begin_pass(sizing)
+            self.x_nhwc = self._buf(H * W * round_up(Cin_img, 4))
+            xin = Act(self.x_nhwc, H, W, Cin_img)
+            table = None
+            if not sizing:
+                Cs = round_up(Cc, 4)
+                table = self._new(2 * Cs)
+                table[:Cs] = 1.0
+                table[Cs:] = 0.0
+            # ---- forward
+            c0 = self._buf(n)
+            self._emit_conv_fwd(self.first, xin, c0, None)
+            self.R0 = R0 = R = TableAct(c0, H, W, Cc, table, self.slope)
+            for k, b in enumerate(self.blocks):
+                c1, c2 = self._buf(n), self._buf(n)
+                self._emit_conv_fwd(b.conv1, R, c1, b.bn1)
+                A1 = Act(c1, H, W, Cc, b.bn1, self.slope)
+                self._emit_conv_fwd(b.conv2, A1, c2, b.bn2)
+                A2 = Act(c2, H, W, Cc, b.bn2, 1.0)
+                b.st = (R, A1, A2)
+                if self.need_residual:
+                    r = self._buf(n)
+                    self._emit_join_fwd(R, A2, r, f"b{k}")
+                    R = Act(r, H, W, Cc)
+                else:
+                    R = A2
+            ct = self._buf(n)
+            self._emit_conv_fwd(self.tail, R, ct, self.tail_bn)
+            T = Act(ct, H, W, Cc, self.tail_bn, 1.0)
+            self.Hout, self.Wout = H, W
+            self.y_out = self._buf(H * W * round_up(oc.Cout, 4))
+            self._emit_conv_fwd(oc, T, self.y_out, None)
+            # ---- backward
+            self.dy_out = self._buf(H * W * round_up(oc.Cout, 4))
+            ops = []
+            self._emit_wgrad(oc, T, self.dy_out, ops)
+            g = self._emit_dgrad(oc, T, self.dy_out, ops, fuse_bn=True)
+            dy = self._emit_bn_act_bwd(T, g, ops)
+            self._emit_wgrad(self.tail, R, dy, ops)
+            G = self._emit_dgrad(self.tail, R, dy, ops, fuse_bn=R.bn is not None)
+            for k in range(len(self.blocks) - 1, -1, -1):
+                b = self.blocks[k]
+                Rk, A1, A2 = b.st
+                dy2 = self._emit_bn_act_bwd(A2, G, ops)
+                self._emit_wgrad(b.conv2, A1, dy2, ops)
+                g1 = self._emit_dgrad(b.conv2, A1, dy2, ops, fuse_bn=True)
+                dy1 = self._emit_bn_act_bwd(A1, g1, ops)
+                self._emit_wgrad(b.conv1, Rk, dy1, ops)
+                gd = self._emit_dgrad(b.conv1, Rk, dy1, ops, fuse_bn=Rk.bn is not None)
+                if self.need_residual:
+                    # the bottom join also applies the derivative of the first activation: its output is dy of conv0
+                    G = self._emit_join_bwd(G, gd, Rk, ops, f"res_join_bwd:b{k}", act_of=R0 if k == 0 else None)
+                else:
+                    G = gd
+            if not (self.need_residual and self.blocks):
+                G = self._emit_join_bwd(None, G, R0, ops, "act_bwd:first", act_of=R0)
+            dy0 = G[0]
+            self._emit_wgrad(self.first, xin, dy0, ops)
+            self.gin = self._emit_dgrad(self.first, xin, dy0, self.bwd_input_ops)
+            self.last_act = T
+            self.bwd_ops = ops
+        self.shape_key = (H, W, Cin_img)
+
+    def forward(self, x: torch.Tensor, head=None):
+        if head is not None:
+            raise NotImplementedError("dip-amd: the fused loss head (utils.loss_head.MSEHead) does not cover the ResNet backbone")
+        if _graph_warmup[0] or (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise NotImplementedError("dip-amd: hipGraph capture (GraphedIteration / optimize(graph=True)) is not implemented "
+                                      "for the ResNet backbone; run it eagerly")
+        return super().forward(x, head)
+
+
+# > 0 while a dip_optim.GraphedIteration runs the eager warm-up iterations of a capture: an engine without a captured form
+# refuses there, before any capture has begun
+_graph_warmup = [0]
 
 
 class _SkipFn(torch.autograd.Function):

@@ -81,6 +81,9 @@ class GroupedFits:
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
             raise RuntimeError("dip-amd: GroupedFits needs nets built by models.skip.skip()")
+        if any(e.kind != "skip" for e in engs):
+            raise NotImplementedError("dip-amd: GroupedFits covers skip() nets only (the ResNet backbone has no grouped "
+                                      "launch list)")
         if device is None:
             device = net_inputs[0].device
         device = torch.device(device)

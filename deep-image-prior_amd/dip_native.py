@@ -188,6 +188,10 @@ _SIGS = {
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dip_fold_to_nchw": (C.c_int, [C.POINTER(DipGradSrc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dip_fold_to_nhwc": (C.c_int, [C.POINTER(DipGradSrc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dip_res_join_fwd": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DipTransform), C.c_void_p, C.c_int, C.POINTER(DipTransform),
+                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dip_res_join_bwd": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(DipGradSrc), C.c_void_p, C.c_int, C.POINTER(DipTransform),
+                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dip_upcat_fwd": (C.c_int, [C.POINTER(DipUpcatDesc), C.c_void_p]),
     "dip_upcat_nblk": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dip_upcat_fwd_fin": (C.c_int, [C.POINTER(DipUpcatDesc), C.POINTER(DipBnFin), C.c_void_p]),

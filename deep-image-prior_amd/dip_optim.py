@@ -231,10 +231,15 @@ class GraphedIteration:
             streams = [self.capture_stream] + self.branch_streams
             for s in streams:
                 s.wait_stream(cur)
-            for _ in range(max(int(warmup), 1)):
-                for (opt, clo), s in zip(self.fits, streams):
-                    with torch.cuda.stream(s):
-                        self._one(opt, clo)
+            import dip_engine
+            dip_engine._graph_warmup[0] += 1          # an engine without a captured form (ResNetEngine) refuses HERE
+            try:
+                for _ in range(max(int(warmup), 1)):
+                    for (opt, clo), s in zip(self.fits, streams):
+                        with torch.cuda.stream(s):
+                            self._one(opt, clo)
+            finally:
+                dip_engine._graph_warmup[0] -= 1
             for s in streams:
                 cur.wait_stream(s)
             torch.cuda.synchronize(device)

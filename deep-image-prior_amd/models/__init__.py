@@ -1,7 +1,10 @@
 """Model factory, API-compatible with the reference's models/__init__.py:8-31.
 
-Only the 'skip' (MI355X-native) and 'identity' nets are provided: the reference's ResNet / UNet /
-texture_nets backbones are outside the accelerated path and raise.
+get_net() provides the 'skip' (MI355X-native) and 'identity' nets; 'ResNet' / 'UNet' / 'texture_nets'
+raise there (the reference's own get_net('ResNet') line is broken).  The ResNet backbone itself is
+native: construct it as the notebooks do, `from models.resnet import ResNet` (models/resnet.py,
+dip_engine.ResNetEngine).  models/unet.py exists so that the notebooks' import cell runs; `UNet(...)`
+raises.
 """
 import torch.nn as nn
 

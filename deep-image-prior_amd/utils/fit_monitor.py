@@ -52,6 +52,9 @@ class FitMonitor:
             eng = getattr(net, "__dict__", {}).get("_dip_engine")
             if eng is None:
                 raise RuntimeError("dip-amd: back-tracking needs a net built by models.skip.skip() (flat parameter arena)")
+            if getattr(eng, "kind", "skip") != "skip":
+                raise NotImplementedError("dip-amd: FitMonitor back-tracking covers skip() nets only; construct it with "
+                                          "backtracking=False for a ResNet")
             self.engine = eng
 
     def update(self, out, loss=None):

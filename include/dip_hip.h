@@ -454,6 +454,22 @@ int dip_fold_to_nchw(const DipGradSrc* src, int H, int W, int C, float* dst, voi
  * between (the stride-1 conv in front of the Lanczos Downsampler of conv(..., downsample_mode='lanczos2')). */
 int dip_fold_to_nhwc(const DipGradSrc* src, int H, int W, int C, float* dst, int Cd, void* stream);
 
+/* Residual join of the ResNet backbone (models/resnet.py:13-24 of the reference: ResidualSequential.forward ends in
+ * `return out + x_`; the crop branch in front of it cannot trigger with the 3x3 / padding-1 convs of get_block):
+ *   out[p][c] = act_a(ta.a[c] * xa[p][c] + ta.b[c]) + act_b(tb.a[c] * xb[p][c] + tb.b[c]),   p < npix, c < C
+ * Both operands are read as raw NHWC conv outputs (channel strides Cxa, Cxb) and transformed on the fly; a transform with
+ * a == NULL is the identity.  C and the strides are multiples of 4.  One read of each input, one write. */
+int dip_res_join_fwd(const float* xa, int Cxa, const DipTransform* ta, const float* xb, int Cxb, const DipTransform* tb,
+                     float* out, int Co, int npix, int C, void* stream);
+/* Its adjoint (autograd AddBackward of the same `out + x_`, models/resnet.py:24) joined with the data gradient of the block's
+ * first conv:  gout = (g + src) [* act'(ty.a[c] * y + ty.b[c])]
+ * g = gradient wrt the block's output ([H][W][Cg], NULL = 0), src = the conv's data gradient where the conv launch left it
+ * (padded / folded: DipGradSrc; no thin-conv source, no crop window).  y != NULL multiplies by the derivative of the
+ * activation behind the net's first conv (models/resnet.py:60-61: conv + act, no BatchNorm in between) at its raw output
+ * y, so the launch at the bottom of the chain writes dy of that conv. */
+int dip_res_join_bwd(const float* g, int Cg, const DipGradSrc* src, const float* y, int Cy, const DipTransform* ty,
+                     float* gout, int Cgo, int H, int W, int C, void* stream);
+
 /* ---------------------------------------------------------------- upsample + concat ------- */
 /* cat[p][0:ns]      = T_s(s[p])                      (skip branch, Concat child "0")
  * cat[p][ns:ns+nd]  = upsample2x(T_d(d))[p]          (deeper branch, nn.Upsample models/skip.py:81)
