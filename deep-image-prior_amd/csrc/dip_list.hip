@@ -51,7 +51,7 @@ const Entry g_fns[] = {
     DIP_REG(dip_maxpool2_fwd), DIP_REG(dip_maxpool2_bwd), DIP_REG(dip_upsample_bwd_stats), DIP_REG(dip_upsample_bwd_stats_crop),
     DIP_REG(dip_upsample_bwd_stats_crop_fin), DIP_REG(dip_upsample_bwd_one),
     DIP_REG(dip_adam_step), DIP_REG(dip_noise_axpy), DIP_REG(dip_adam_tick), DIP_REG(dip_adam_step_dev),
-    DIP_REG(dip_noise_axpy_dev), DIP_REG(dip_noise_axpy_dev2), DIP_REG(dip_counter_add),
+    DIP_REG(dip_noise_axpy_dev), DIP_REG(dip_noise_axpy_dev2), DIP_REG(dip_counter_add), DIP_REG(dip_counter_add_n),
     DIP_REG(dip_loss_head_fwd), DIP_REG(dip_loss_head_bwd), DIP_REG(dip_fit_monitor), DIP_REG(dip_arena_backtrack),
     DIP_REG(dip_lanczos_down_fwd), DIP_REG(dip_lanczos_down_bwd), DIP_REG(dip_down_dense_fwd), DIP_REG(dip_down_dense_bwd_data),
     DIP_REG(dip_down_dense_bwd_weight), DIP_REG(dip_res_join_fwd), DIP_REG(dip_res_join_bwd),
@@ -94,6 +94,30 @@ extern "C" int dip_list_run(const DipCmd* cmds, int n, void* const* streams, int
             else if (rc == -1 && (c.fn < 0 || c.fn >= NFN || c.slots == nullptr || c.nslots != g_fns[c.fn < 0 || c.fn >= NFN ? 0 : c.fn].nargs))
                 dip_set_error("list_run: malformed LAUNCH command (function id, slot count)");
             else if (c.kind != DIP_CMD_LAUNCH) dip_set_error(hipGetErrorString((hipError_t)rc));
+            return rc;
+        }
+    }
+    return 0;
+}
+
+// One optimisation iteration as ONE call: the command lists of its phases (reg-noise + weight repack + input layout, the forward
+// list, the fused loss head, the backward list, Adam) issued back to back on one stream table.  Every phase brings its own event
+// table, so the lists are the very arrays dip_list_run issues phase by phase: same launches, same order, same fork / join events.
+extern "C" int dip_iter_run(const DipPhase* phases, int nphases, void* const* streams, int nstreams, int* failed_at) {
+    if (failed_at != nullptr) failed_at[0] = failed_at[1] = -1;
+    if (phases == nullptr || nphases < 0 || streams == nullptr || nstreams < 1) {
+        dip_set_error("iter_run: needs a phase table and at least one stream");
+        return -1;
+    }
+    for (int p = 0; p < nphases; ++p) {
+        const DipPhase& ph = phases[p];
+        int at = -1;
+        int rc = -1;
+        if (ph.n < 0 || (ph.n > 0 && ph.cmds == nullptr) || ph.nevents < 0 || (ph.nevents > 0 && ph.events == nullptr))
+            dip_set_error("iter_run: malformed phase (command / event table)");
+        else rc = dip_list_run(ph.cmds, ph.n, streams, nstreams, ph.events, ph.nevents, &at);
+        if (rc != 0) {
+            if (failed_at != nullptr) { failed_at[0] = p; failed_at[1] = at; }
             return rc;
         }
     }

@@ -260,6 +260,13 @@ __global__  void counter_add_kernel(unsigned long long* c_, unsigned long long i
     if (threadIdx.x == 0 && blockIdx.x == 0) *c += inc;
 }
 
+template <bool GRP = false>
+__global__  void counter_add_n_kernel(unsigned long long* c_, int n, unsigned long long inc, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(unsigned long long*, c);
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) c[i] += inc;
+}
+
 }  // namespace
 
 // the coalesced head needs a lane per output channel inside a pixel's lane group
@@ -320,6 +327,14 @@ extern "C" int dip_adam_tick(DipIterState* st, double lr, double beta1, double b
 extern "C" int dip_counter_add(uint64_t* counter, uint64_t inc, void* stream) {
     dip_launch_pair<DIP_FAM_LOSS>(counter_add_kernel<false>, counter_add_kernel<true>, dim3(1), dim3(1), 0, (hipStream_t)stream,
                                   reinterpret_cast<unsigned long long*>(counter), (unsigned long long)inc);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_counter_add_n(uint64_t* counters, int n, uint64_t inc, void* stream) {
+    if (counters == nullptr || n < 1) DIP_FAIL("counter_add_n: needs n >= 1 counters");
+    dip_launch_pair<DIP_FAM_LOSS>(counter_add_n_kernel<false>, counter_add_n_kernel<true>, dim3(dip_cdiv(n, 64)), dim3(64), 0,
+                                  (hipStream_t)stream, reinterpret_cast<unsigned long long*>(counters), n, (unsigned long long)inc);
     DIP_CHECK_LAUNCH();
     return 0;
 }

@@ -1094,9 +1094,10 @@ class SkipEngine:
             st_ = self._aux[(slot, self.device)] = ([torch.cuda.Stream(self.device) for _ in range(3)], {})
         return slot, st_[0], st_[1]
 
-    def _issue(self, ops, main, key, cls_fn=None, join_before_fn=None, deps=None):
+    def _issue(self, ops, main, key, cls_fn=None, join_before_fn=None, deps=None, compile_only=False):
         """Issues a launch list: compiled once per (key, length) into a command list and run by ONE dip_list_run call, or
-        (DIP_NO_CLIST=1) walked in Python with torch events -- the same schedule either way."""
+        (DIP_NO_CLIST=1) walked in Python with torch events -- the same schedule either way.
+        compile_only: nothing is issued; returns the compiled command list (None under DIP_NO_CLIST=1)."""
         multi = cls_fn is not None
         slot, aux, events = self._aux_streams() if multi else ("one", [], None)
         ko = False
@@ -1124,6 +1125,8 @@ class SkipEngine:
                 cl = N.CmdList(cmds)
             ent = self._clists[ck] = (sched, cl)
         sched, cl = ent
+        if compile_only:
+            return cl
         if cl is not None:
             cl.run([main.cuda_stream] + [s_.cuda_stream for s_ in aux], slot)
             return
@@ -1144,11 +1147,11 @@ class SkipEngine:
             else:
                 streams[c[1]].wait_event(events[(key, c[2])])
 
-    def _run(self, ops, main, key="one"):
-        self._issue(ops, main, key)
+    def _run(self, ops, main, key="one", compile_only=False):
+        return self._issue(ops, main, key, compile_only=compile_only)
 
-    def _run_two_streams(self, ops, main, cls_fn, join_before_fn, key, deps=None):
-        self._issue(ops, main, key, cls_fn, join_before_fn, deps)
+    def _run_two_streams(self, ops, main, cls_fn, join_before_fn, key, deps=None, compile_only=False):
+        return self._issue(ops, main, key, cls_fn, join_before_fn, deps, compile_only)
 
     # stream class of a backward op: 2 = bulk (weight gradients), 1 = side, 0 = main
     _BWD_SIDE = staticmethod(lambda n: 2 if n.startswith(("wgrad:", "wgred:")) else
@@ -1186,7 +1189,7 @@ class SkipEngine:
             # (no main-stream op behind it: the final join of _run_two_streams covers it)
         return deps
 
-    def _run_backward_two_streams(self, ops, main):
+    def _run_backward_two_streams(self, ops, main, compile_only=False):
         deps = self._bwd_deps if getattr(self, "_bwd_deps_for", None) is ops else None
         if deps is None:
             deps = self._bwd_deps = self._backward_deps(ops)
@@ -1197,36 +1200,57 @@ class SkipEngine:
         capturing = torch.cuda.is_current_stream_capturing()
         bulk2 = self._bulk2 if not capturing else ()
         cls = self._BWD_SIDE if not bulk2 else (lambda n: 3 if n in bulk2 else self._BWD_SIDE(n))
-        self._run_two_streams(ops, main, cls, lambda n: False, "bwd_cap" if capturing else "bwd", deps)
+        return self._run_two_streams(ops, main, cls, lambda n: False, "bwd_cap" if capturing else "bwd", deps, compile_only)
 
-    def _run_forward_two_streams(self, ops, main):
+    def _run_forward_two_streams(self, ops, main, compile_only=False):
         side = self._fwd_side
-        self._run_two_streams(ops, main, lambda n: 1 if n in side else 0, lambda n: n.startswith("upcat:"), "fwd")
+        return self._run_two_streams(ops, main, lambda n: 1 if n in side else 0, lambda n: n.startswith("upcat:"), "fwd",
+                                     compile_only=compile_only)
 
-    def _launch_forward(self, x_ptr, main, with_out_conv=True):
+    def _forward_prologue(self, x_ptr):
+        """The launches in front of the forward list, as (fn, args, name): weight repack, NCHW -> NHWC of the input at x_ptr."""
+        lib = self.lib
+        ops = [(lib.dip_pack_weights, (_ptr(self.params), _ptr(self.packed), self.pack_recs.data_ptr(),
+                                       len(self.convs), self.pack_max), "pack_weights")]
+        if self.bf3:
+            ops.append((lib.dip_pack_weights_bf3, (_ptr(self.params), self.packed3.data_ptr(), self.pack_recs3.data_ptr(),
+                                                   len(self.convs), self.pack_max3), "pack_weights_bf3"))
+        ops.append((lib.dip_nchw_to_nhwc, (x_ptr, _ptr(self.x_nhwc), self.Cimg, self.H * self.W, round_up(self.Cimg, 4)),
+                    "nchw_to_nhwc"))
+        return ops
+
+    def _launch_forward(self, x_ptr, main, with_out_conv=True, compile_only=False):
         """The static forward launch list on stream `main` (+ the side stream): weight repack, NCHW -> NHWC of the input
         at x_ptr, every layer up to (with_out_conv: and including) the output conv.  Pointers only -- also what
-        dip_group.GroupedFits issues once for B instances."""
-        lib, stream = self.lib, main.cuda_stream
-        N.check(lib.dip_pack_weights(_ptr(self.params), _ptr(self.packed), self.pack_recs.data_ptr(),
-                                     len(self.convs), self.pack_max, stream), "pack_weights")
-        if self.bf3:
-            N.check(lib.dip_pack_weights_bf3(_ptr(self.params), self.packed3.data_ptr(), self.pack_recs3.data_ptr(),
-                                             len(self.convs), self.pack_max3, stream), "pack_weights_bf3")
-        N.check(lib.dip_nchw_to_nhwc(x_ptr, _ptr(self.x_nhwc), self.Cimg, self.H * self.W, round_up(self.Cimg, 4), stream),
-                "nchw_to_nhwc")
+        dip_group.GroupedFits issues once for B instances.
+        compile_only: issues nothing and returns the compiled command list of the layers (the prologue is not part of it)."""
+        if not compile_only:
+            stream = main.cuda_stream
+            for fn, args, name in self._forward_prologue(x_ptr):
+                N.check(fn(*args, stream), name)
         ops = self.fwd_ops if with_out_conv else self.fwd_ops[:-1]      # the last op is the output conv
         if self.two_streams:
-            self._run_forward_two_streams(ops, main)
-        else:
-            self._run(ops, main, "fwd1")
+            return self._run_forward_two_streams(ops, main, compile_only)
+        return self._run(ops, main, "fwd1", compile_only)
 
-    def _launch_backward(self, main):
+    def _launch_backward(self, main, compile_only=False):
         """The static backward launch list (dy of the output conv already in self.dy_out)."""
         if self.two_streams:
-            self._run_backward_two_streams(self.bwd_ops, main)
-        else:
-            self._run(self.bwd_ops, main, "bwd1")
+            return self._run_backward_two_streams(self.bwd_ops, main, compile_only)
+        return self._run(self.bwd_ops, main, "bwd1", compile_only)
+
+    def iteration_lists(self):
+        """(forward list without the output conv, backward list) of the current plan as the compiled command lists an eager
+        closure with the fused loss head issues -- the same objects, so a caller that chains them (dip_optim.NativeIteration:
+        one dip_iter_run call per iteration) launches exactly what forward(x, head) + backward() launch.  They live until
+        _build_plan resets self._clists; a caller must not keep them beyond that (compare `self._clists` by identity)."""
+        if not self.use_clist:
+            raise RuntimeError("dip-amd: the native iteration chains compiled command lists; DIP_NO_CLIST=1 switches them off")
+        if self._knockout is not None:
+            raise RuntimeError("dip-amd: DIP_KNOCKOUT is a timing experiment of the eager path; the native iteration refuses it")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dip-amd: the native iteration is an eager form; hipGraph capture goes through GraphedIteration")
+        return self._launch_forward(None, None, False, compile_only=True), self._launch_backward(None, compile_only=True)
 
     def _net_cin(self) -> int:
         return self.sc[0].down_a.Cin

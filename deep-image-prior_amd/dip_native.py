@@ -90,6 +90,10 @@ class DipCmd(C.Structure):
                 ("slots", C.POINTER(C.c_uint64)), ("nslots", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DipPhase(C.Structure):
+    _fields_ = [("cmds", C.POINTER(DipCmd)), ("events", C.POINTER(C.c_void_p)), ("n", C.c_int32), ("nevents", C.c_int32)]
+
+
 class DipIterState(C.Structure):
     _fields_ = [("step", C.c_uint64), ("step_size", C.c_float), ("bc2_sqrt", C.c_float)]
 
@@ -110,6 +114,7 @@ _SIGS = {
     "dip_list_fn_nargs": (C.c_int, [C.c_int]),
     "dip_list_run": (C.c_int, [C.POINTER(DipCmd), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int,
                                C.POINTER(C.c_int)]),
+    "dip_iter_run": (C.c_int, [C.POINTER(DipPhase), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "dip_events_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "dip_events_destroy": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "dip_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -225,6 +230,7 @@ _SIGS = {
     "dip_noise_axpy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p]),
     "dip_noise_axpy_dev2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
     "dip_counter_add": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "dip_counter_add_n": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
     "dip_group_begin": (C.c_int, [C.c_int, C.c_longlong, C.c_void_p, C.c_longlong]),
     "dip_group_end": (C.c_int, []),
     "dip_group_size": (C.c_int, []),
@@ -410,3 +416,33 @@ class CmdList:
                     lib().dip_events_destroy(ev, self.nevents)
         except Exception:
             pass
+
+
+class IterList:
+    """The phases of one optimisation iteration (CmdList objects, issued in order) behind ONE dip_iter_run call.  The phases
+    keep their own event sets (`key` as in CmdList.run); the stream table is shared: run(stream_ptrs)."""
+
+    def __init__(self, phases, key="eager"):
+        self.phases = list(phases)                 # (keeps the command arrays, their slots and events alive)
+        self.arr = (DipPhase * max(len(self.phases), 1))()
+        for i, cl in enumerate(self.phases):
+            ev = cl._event_set(key)
+            self.arr[i] = DipPhase(C.cast(cl.arr, C.POINTER(DipCmd)), C.cast(ev, C.POINTER(C.c_void_p)), cl.n, cl.nevents)
+        self.n = len(self.phases)
+        self._failed = (C.c_int * 2)(-1, -1)
+        self._streams = None
+        self._stream_key = None
+        self._run = lib().dip_iter_run
+
+    def run(self, stream_ptrs):
+        if stream_ptrs != self._stream_key:
+            self._streams = (C.c_void_p * len(stream_ptrs))(*stream_ptrs)
+            self._stream_key = list(stream_ptrs)
+        rc = self._run(self.arr, self.n, self._streams, len(stream_ptrs), self._failed)
+        if rc:
+            p, k = self._failed[0], self._failed[1]
+            name = "iter_run"
+            if 0 <= p < self.n:
+                names = self.phases[p].names
+                name = f"phase {p}: " + (names[k] if 0 <= k < len(names) else "list_run")
+            check(rc, name)

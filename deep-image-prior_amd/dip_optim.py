@@ -12,9 +12,14 @@ static launch sequence: `GraphedIteration` captures {zero_grad(); closure(); ste
 hipGraph and replays it.  Several independent fits: `GraphedIteration.group(dip_group.GroupedFits(...))`
 captures ONE launch list that serves all of them (every kernel launch covers all instances), and
 `GraphedIteration.group([(optimizer, closure), ...])` -- arbitrary closures -- one graph per fit on its own stream.
+
+`NativeIteration` is the eager form without autograd: head (utils.loss_head.MSEHead), reg-noise (utils.reg_noise.RegNoise) and
+optimiser known statically, the whole iteration -- noise, forward list, loss head, backward list, Adam -- is ONE call into
+the library (dip_iter_run), bit-identical to {zero_grad(); closure(); step()} and interchangeable with it at any iteration.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import torch
@@ -135,10 +140,7 @@ class FusedAdam:
             dev = g.params[0].device
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
-                st = self._iter_state.get(dev)
-                if st is None:
-                    st = self._iter_state[dev] = torch.zeros(16, dtype=torch.uint8, device=dev)
-                    st.view(torch.int64)[0] = self.step_count - 1
+                st = self._state(dev, self.step_count - 1)
                 if dev not in ticked:          # t <- t + 1, step_size and sqrt(bc2) in double, on the device
                     N.check(lib.dip_adam_tick(st.data_ptr(), float(self.lr), float(self.betas[0]),
                                               float(self.betas[1]), stream), "adam_tick")
@@ -147,6 +149,14 @@ class FusedAdam:
                                               float(self.betas[0]), float(self.betas[1]), float(self.eps),
                                               st.data_ptr(), stream), "adam_step_dev")
         return loss
+
+    def _state(self, dev, step):
+        """The DipIterState of device `dev`; created holding `step` (the count before the step about to be taken)."""
+        st = self._iter_state.get(dev)
+        if st is None:
+            st = self._iter_state[dev] = torch.zeros(16, dtype=torch.uint8, device=dev)
+            st.view(torch.int64)[0] = step
+        return st
 
     def device_step_count(self):
         """Adam's step count as the device holds it (after graph replays the host count is stale)."""
@@ -279,6 +289,212 @@ class GraphedIteration:
             for m in self.members:
                 cur.wait_stream(m.capture_stream)
         self.iterations += int(n)
+
+
+class NativeIteration:
+    """One optimisation iteration of a skip() net under the fused loss head, without autograd: exactly
+
+        opt.zero_grad()
+        x = reg_noise() if reg_noise else net_input
+        loss, out = head(x)
+        loss.backward()
+        opt.step()
+
+    -- the body of the reference's optimize() loop (utils/common_utils.py:223-230) around the closure of
+    inpainting.ipynb:300-315 / denoising.ipynb:204-221 -- issued by ONE call into the library (dip_iter_run): the reg-noise
+    launch, the engine's forward command list, dip_loss_head_fwd, the BatchNorm batch counters, dip_loss_head_bwd, the engine's
+    backward command list, dip_adam_tick + dip_adam_step_dev.  The two lists are the objects the eager path issues (same
+    launches, same two-stream schedule, same events), so the results are bit-identical and the two forms may be mixed on the same
+    net / head / optimiser at any iteration boundary.  No autograd node is built, nothing synchronises.
+
+        head = MSEHead(net, target, mask=mask_or_None)
+        opt = FusedAdam(get_params('net', net, net_input), lr=LR)
+        it = NativeIteration(net, head, opt, net_input, reg_noise=RegNoise(net_input, std) or None)
+        loss = it.step()          # 0-dim device tensor
+        losses = it.run(n)        # device tensor [n]
+        it.out                    # the last network output [1,C,H,W], detached (a buffer this object owns and overwrites)
+
+    The command arrays are built once and rebuilt when the engine re-plans (input size, re-typed net), when the optimiser's
+    parameters move or lr / betas / eps change, and when the head's target / mask or the noise settings are replaced.  Every
+    slot of them is iteration-invariant; the ONE value that changes per iteration -- where the loss scalar goes -- is a field
+    of the loss-head descriptor this object owns, which the library reads when it launches."""
+
+    def __init__(self, net, head, optimizer, net_input, reg_noise=None):
+        import dip_group
+        from utils.loss_head import MSEHead
+        from utils.reg_noise import RegNoise
+        if isinstance(net, dip_group.GroupedFits) or isinstance(head, dip_group.GroupedFits):
+            raise NotImplementedError("dip-amd: NativeIteration drives ONE fit; grouped fits run through "
+                                      "GraphedIteration.group(GroupedFits(...))")
+        eng = getattr(net, "__dict__", {}).get("_dip_engine")
+        if eng is None or isinstance(eng, Exception):
+            raise RuntimeError("dip-amd: NativeIteration needs a net built by models.skip.skip()")
+        if eng.kind != "skip":
+            raise NotImplementedError("dip-amd: NativeIteration covers skip() nets; the ResNet backbone has no fused loss head "
+                                      "(run it through the eager closure)")
+        if not net.training:
+            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
+        if not isinstance(optimizer, FusedAdam):
+            raise TypeError(f"dip-amd: NativeIteration needs a dip_optim.FusedAdam, got {type(optimizer).__name__}")
+        want = eng.param_list
+        if len(optimizer.params) != len(want) or any(a is not b for a, b in zip(optimizer.params, want)):
+            raise ValueError("dip-amd: NativeIteration steps exactly the net's parameters (get_params('net', ...)); "
+                             "opt_over with 'input' or 'down' goes through the eager closure")
+        if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
+            raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
+                               "fallback)")
+        if net_input.dim() != 4 or net_input.shape[0] != 1 or net_input.dtype != torch.float32 \
+                or not net_input.is_contiguous():
+            raise ValueError(f"dip-amd: net_input must be a contiguous fp32 [1,C,H,W] tensor, got {net_input.dtype} "
+                             f"{tuple(net_input.shape)}")
+        if net_input.requires_grad:
+            raise ValueError("dip-amd: net_input requires grad (opt_over='net,input'): that goes through the eager closure")
+        if not isinstance(head, MSEHead):
+            raise TypeError(f"dip-amd: NativeIteration needs a utils.loss_head.MSEHead, got {type(head).__name__}")
+        if head.net is not net:
+            raise ValueError("dip-amd: the MSEHead was built for another net")
+        if reg_noise is not None:
+            if not isinstance(reg_noise, RegNoise):
+                raise TypeError("dip-amd: reg_noise must be a utils.reg_noise.RegNoise or None, got "
+                                f"{type(reg_noise).__name__}")
+            if reg_noise.saved.shape != net_input.shape or reg_noise.saved.device != net_input.device:
+                raise ValueError("dip-amd: the RegNoise was built for another net_input")
+        self.net, self.head, self.opt, self.engine = net, head, optimizer, eng
+        self.net_input, self.reg = net_input.detach(), reg_noise
+        self.device = net_input.device
+        self.out = None
+        self.iterations = 0
+        self._key = None
+        self._plan = None
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device)      # d loss / d loss, as autograd seeds backward()
+        self._check_capture()
+
+    def _check_capture(self):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dip-amd: NativeIteration.step() cannot be captured into a hipGraph (its loss slot changes per "
+                               "iteration); capture the eager closure with GraphedIteration instead")
+
+    # -------------------------------------------------------------------------------------------- the command arrays
+    def _signature(self, sig):
+        """Everything a slot of the command arrays was computed from.  Objects by identity: the arrays hold raw pointers, and
+        the plan keeps every object of its key alive, so neither an id nor an address can be recycled unnoticed."""
+        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
+        # (an engine that has never planned has no op lists yet: None never equals a built key)
+        return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
+                opt.lr, opt.betas, opt.eps, id(opt._groups),
+                id(head.target), head.target.data_ptr(), id(head.mask), head.mask_c,
+                None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset)))
+
+    def _build(self):
+        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
+        lib = N.lib()
+        dev = self.device
+        noisy = reg is not None and reg.std > 0
+        x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
+        _, Cimg, H, W = x.shape
+        # the engine's own preparation, as SkipEngine.forward does it
+        if eng.device != dev or not eng._arena_ok():
+            eng._build_arenas(dev)
+        if eng.shape_key != (H, W, Cimg):
+            if Cimg != eng._net_cin():
+                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {eng._net_cin()}")
+            eng._build_plan(H, W, Cimg)
+        if opt._sig != opt._signature():
+            opt._prepare()
+        fwd, bwd = eng.iteration_lists()
+        out = self.out
+        if out is None or tuple(out.shape) != (1, eng.n_out, eng.Hout, eng.Wout) or out.device != dev:
+            out = torch.empty((1, eng.n_out, eng.Hout, eng.Wout), dtype=torch.float32, device=dev)
+        loss0 = torch.zeros((), dtype=torch.float32, device=dev)
+        desc = head._descriptor(eng, out, loss0)
+        pre = []
+        if noisy:
+            pre.append((lib.dip_noise_axpy_dev, (reg.saved.data_ptr(), reg.out.data_ptr(), reg.saved.numel(), reg.std,
+                                                 reg.seed, reg.offset.data_ptr()), "noise_axpy_dev"))
+        pre += eng._forward_prologue(x.data_ptr())
+        mid = [(lib.dip_loss_head_fwd, (C.byref(desc),), "loss_head_fwd")]
+        if len(eng.bns):
+            mid.append((lib.dip_counter_add_n, (eng.nbt.data_ptr(), eng.nbt.numel(), 1), "num_batches_tracked"))
+        mid.append((lib.dip_loss_head_bwd, (C.byref(desc), self._one.data_ptr(), eng.dy_out.data_ptr(),
+                                            N.round_up(eng.n_out, 4)), "loss_head_bwd"))
+        st = opt._state(dev, opt.step_count)
+        b1, b2 = float(opt.betas[0]), float(opt.betas[1])
+        adam = [(lib.dip_adam_tick, (st.data_ptr(), float(opt.lr), b1, b2), "adam_tick")]
+        pbase, gbase = eng.params.data_ptr(), eng.grads.data_ptr()
+        for g in opt._groups:
+            if g.params[0].device != dev or g.base < pbase or g.base + 4 * g.numel > pbase + 4 * eng.params.numel():
+                raise RuntimeError("dip-amd: a FusedAdam group lies outside the net's parameter arena")
+            # the gradient arena mirrors the parameter arena: the group's gradients are flat at the same offset
+            adam.append((lib.dip_adam_step_dev, (g.base, gbase + (g.base - pbase), g.m.data_ptr(), g.v.data_ptr(), g.numel,
+                                                 b1, b2, float(opt.eps), st.data_ptr()), "adam_step_dev"))
+        on_main = lambda ops: N.CmdList([("launch", fn, args, 0, name) for fn, args, name in ops])
+        lists = N.IterList([on_main(pre), fwd, on_main(mid), bwd, on_main(adam)])
+        views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]
+        self.out = out
+        # everything a slot points to stays alive with the plan, and so does every object whose id is part of the key
+        self._plan = dict(lists=lists, desc=desc, views=views, x=x, state=st, loss0=loss0, scratch=head._scratch,
+                          keep=(head.target, head.mask, head._keep, eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
+                                eng.params, eng.grads, eng.nbt, eng.dy_out,
+                                None if reg is None else (reg.saved, reg.out, reg.offset)))
+        self._key = self._signature(opt._sig)
+
+    # -------------------------------------------------------------------------------------------- run
+    def _begin(self):
+        if not self.net.training:
+            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
+        self._check_capture()
+        # (the parameters' addresses are part of the key: they also say that the engine's arena still holds the parameters)
+        if self._signature(self.opt._signature()) != self._key:
+            self._build()
+        eng = self.engine
+        ptrs = [torch.cuda.current_stream(self.device).cuda_stream]
+        if eng.two_streams:
+            ptrs += [s_.cuda_stream for s_ in eng._aux_streams()[1]]
+        return ptrs
+
+    def _issue(self, loss_ptr, ptrs):
+        self._plan["desc"].loss = loss_ptr        # read by dip_loss_head_fwd when it launches
+        self._plan["lists"].run(ptrs)
+
+    def _finish(self, n):
+        eng = self.engine
+        for p, v in zip(eng.param_list, self._plan["views"]):      # what autograd leaves after zero_grad() + backward()
+            if p.grad is not v:
+                p.grad = v
+        eng.fwd_id += n                           # (a pending autograd backward of an earlier eager forward is stale now)
+        eng.last_out, eng.last_head = self.out, self.head
+        self.opt.step_count += n
+        self.iterations += n
+
+    @torch.no_grad()
+    def step(self):
+        """One iteration; returns the loss as a 0-dim device tensor (no host synchronisation)."""
+        with torch.cuda.device(self.device):
+            ptrs = self._begin()
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+            self._issue(loss.data_ptr(), ptrs)
+            self._finish(1)
+        return loss
+
+    @torch.no_grad()
+    def run(self, n):
+        """n iterations; returns their losses as a device tensor [n] (no host synchronisation inside)."""
+        n = max(int(n), 0)
+        with torch.cuda.device(self.device):
+            losses = torch.empty(n, dtype=torch.float32, device=self.device)
+            if n == 0:
+                return losses
+            ptrs = self._begin()
+            base = losses.data_ptr()
+            done = 0
+            try:
+                for i in range(n):
+                    self._issue(base + 4 * i, ptrs)
+                    done += 1
+            finally:
+                if done:
+                    self._finish(done)
+        return losses
 
 
 class ArenaLBFGS:

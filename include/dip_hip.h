@@ -78,6 +78,23 @@ int dip_list_run(const DipCmd* cmds, int n, void* const* streams, int nstreams, 
 int dip_events_create(void** events, int n);
 int dip_events_destroy(void** events, int n);
 
+/* One optimisation iteration as ONE call -- the body of the reference's loop, `optimizer.zero_grad(); closure();
+ * optimizer.step()` (utils/common_utils.py:223-230) around the closure of inpainting.ipynb:300-315 / denoising.ipynb:204-221
+ * (reg-noise, net(net_input), masked MSE, backward()) -- once the head, the noise and the optimiser are known statically:
+ * the command lists of its phases (reg-noise + weight repack + input layout | forward list | dip_loss_head_fwd, BatchNorm
+ * batch counters, dip_loss_head_bwd | backward list | dip_adam_tick + dip_adam_step_dev) issued back to back on ONE stream
+ * table.  No autograd graph, no per-phase foreign call.  A phase is a command array as dip_list_run takes it plus the event
+ * table ITS records / waits index (phases do not share events), so the forward / backward phases are the arrays the
+ * engine issues through dip_list_run: same launches, same order, same fork / join events.  Allocates nothing, never
+ * synchronises.  Returns 0, or the rc of the first failing command with failed_at[0] = its phase, failed_at[1] = its index
+ * in that phase (failed_at: int[2] or NULL).  Python wrapper: dip_native.IterList, used by dip_optim.NativeIteration. */
+typedef struct DipPhase {
+    const DipCmd* cmds;
+    void* const* events;
+    int32_t n, nevents;
+} DipPhase;
+int dip_iter_run(const DipPhase* phases, int nphases, void* const* streams, int nstreams, int* failed_at);
+
 /* ---------------------------------------------------------------- grouped execution --------- */
 /* B independent fits in ONE launch list: B copies of the skip-net of models/skip.py:45-100 --
  * own weights, own BatchNorm statistics, own Adam state, own input and target -- with identical architecture and sizes.
@@ -571,6 +588,9 @@ int dip_noise_axpy_dev(const float* z, float* out, int64_t n, float sigma, uint6
 int dip_noise_axpy_dev2(const float* z, float* out, int64_t n, float sigma, uint64_t* state_dev, void* stream);
 /* *counter += inc (one thread; ordering by the stream). */
 int dip_counter_add(uint64_t* counter, uint64_t inc, void* stream);
+/* counters[i] += inc for i < n in one launch: `num_batches_tracked += 1` of every nn.BatchNorm2d of the net in train mode
+ * (models/common.py:82,95 through torch.nn.BatchNorm2d.forward), whose counters the engine keeps in one int64 arena. */
+int dip_counter_add_n(uint64_t* counters, int n, uint64_t inc, void* stream);
 
 /* ---------------------------------------------------------------- fused loss head ------------ */
 /* The tail of the closure in two launches: output conv (1x1, Cout <= 4, weights straight from the

@@ -1,0 +1,150 @@
+"""dip_optim.NativeIteration (the whole iteration as ONE dip_iter_run call, no autograd) against the eager MSEHead closure
+
+    opt.zero_grad(); x = reg(); loss, out = head(x); loss.backward(); opt.step()
+
+for bench.py's `default` (512 x 512, reg-noise 1/30) and `library` (448 x 704, masked MSE) configurations.
+
+    python tools/bench_native_iter.py [--configs default library] [--blocks 5] [--iters 50] [--out profiles/NAME.json]
+
+Per configuration two nets are built from one seed; blocks of `--iters` iterations alternate between the two forms (A B A B
+..., `--blocks` of each) in ONE process on one card.  Per block and iteration:
+  * wall       -- first call until the closing synchronize() returns;
+  * host_issue -- first call until the last step() returns, BEFORE the closing synchronize() (when the GPU is the limit and
+                  the launch queue fills, this tends towards the wall time: read it next to `wall`).
+Medians, minima and maxima over the blocks, and a final check that the two nets are still bit-identical.
+Every configuration runs in a child process of its own under `timeout`, the children chained with `&&`; one JSON file.
+"""
+import argparse
+import json
+import os
+import shlex
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+
+def _stats(v):
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4),
+            "blocks": [round(x, 4) for x in v]}
+
+
+def child(config, blocks, iters, warmup, out_path):
+    import torch          # before the library: libdip_hip.so must bind to the HIP runtime torch has loaded
+    ge.build()
+    import bench
+    import dip_native
+    from dip_optim import FusedAdam, NativeIteration
+    from utils.common_utils import get_params
+    from utils.loss_head import MSEHead
+    from utils.reg_noise import RegNoise
+    assert torch.cuda.is_available(), "bench_native_iter.py needs an MI355X"
+    dev = torch.device("cuda:0")
+    size = bench.CONFIGS[config]["size"]
+    reg_std = {"default": 1. / 30., "library": 0.0}[config]
+
+    def make():
+        torch.manual_seed(0)
+        net, depth = bench.build_net(config)
+        net = net.to(dev)
+        z, target = bench.make_problem(0, size, depth)
+        z, target = z.to(dev), target.to(dev)
+        mask = None
+        if config == "library":
+            g = torch.Generator().manual_seed(1000)
+            mask = (torch.rand(1, 1, *size, generator=g) > 0.3).float().expand(1, 3, *size).contiguous().to(dev)
+        head = MSEHead(net, target, mask)
+        reg = RegNoise(z, reg_std, seed=1234) if reg_std > 0 else None
+        opt = FusedAdam(get_params('net', net, z), lr=0.01)
+        return net, z, head, reg, opt
+
+    net_a, z_a, head_a, reg_a, opt_a = make()
+    net_b, z_b, head_b, reg_b, opt_b = make()
+    last = {}
+
+    def eager():
+        opt_a.zero_grad()
+        loss, out = head_a(reg_a() if reg_a is not None else z_a)
+        loss.backward()
+        opt_a.step()
+        last["out"] = out
+
+    it = NativeIteration(net_b, head_b, opt_b, z_b, reg_noise=reg_b)
+    for _ in range(warmup):
+        eager()
+        it.step()
+    torch.cuda.synchronize()
+    res = {k: {"wall": [], "host": []} for k in ("eager", "native")}
+    for _ in range(blocks):
+        for name, one in (("eager", eager), ("native", it.step)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                one()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            res[name]["host"].append((t1 - t0) / iters * 1e3)
+            res[name]["wall"].append((t2 - t0) / iters * 1e3)
+    same = all(torch.equal(p, q) for p, q in zip(net_a.parameters(), net_b.parameters())) and torch.equal(last["out"], it.out)
+    eng = net_b.__dict__["_dip_engine"]
+    rec = {
+        "config": config, "size": list(size), "blocks": blocks, "iters_per_block": iters, "warmup": warmup,
+        "launches_per_iteration": sum(1 for cl in it._plan["lists"].phases for n in cl.names if n not in ("record", "wait")),
+        "two_streams": bool(eng.two_streams),
+        "eager_ms": {"wall": _stats(res["eager"]["wall"]), "host_issue": _stats(res["eager"]["host"])},
+        "native_ms": {"wall": _stats(res["native"]["wall"]), "host_issue": _stats(res["native"]["host"])},
+        "bit_identical_after_run": bool(same),
+        "device": torch.cuda.get_device_name(0), "build_id": dip_native.lib().dip_build_id().decode(),
+    }
+    e, n = rec["eager_ms"], rec["native_ms"]
+    rec["host_issue_ratio_eager_over_native"] = round(e["host_issue"]["median"] / n["host_issue"]["median"], 3)
+    rec["wall_ratio_eager_over_native"] = round(e["wall"]["median"] / n["wall"]["median"], 3)
+    rec["it_per_s"] = {"eager": round(1e3 / e["wall"]["median"], 1), "native": round(1e3 / n["wall"]["median"], 1)}
+    with open(out_path, "w") as f:
+        json.dump(rec, f)
+    print(json.dumps(rec))
+    if not same:
+        raise SystemExit("the two forms diverged")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", nargs="+", default=["default", "library"], choices=["default", "library"])
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per configuration")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "native_iter_bench.json"))
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.blocks < 5 or args.iters < 50:
+        ap.error("at least 5 blocks of at least 50 iterations")
+    if args.child is not None:
+        child(args.child, args.blocks, args.iters, args.warmup, args.out)
+        return
+    parts = {c: f"{args.out}.{c}.part" for c in args.configs}
+    steps = [" ".join(["timeout", "-k", "10", str(args.timeout), shlex.quote(sys.executable), shlex.quote(os.path.abspath(__file__)),
+                       "--child", c, "--blocks", str(args.blocks), "--iters", str(args.iters), "--warmup", str(args.warmup),
+                       "--out", shlex.quote(p)]) for c, p in parts.items()]
+    rc = subprocess.run(["bash", "-c", " && ".join(steps)]).returncode          # a failing step ends the chain
+    done = {}
+    for c, p in parts.items():
+        if os.path.exists(p):
+            with open(p) as f:
+                done[c] = json.load(f)
+            os.remove(p)
+    if done:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/bench_native_iter.py", "results": done}, f, indent=1)
+            f.write("\n")
+    if rc:
+        raise SystemExit(f"a configuration failed (exit status {rc}); results so far: {sorted(done)}")
+
+
+if __name__ == "__main__":
+    main()
