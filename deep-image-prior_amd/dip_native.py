@@ -105,6 +105,13 @@ class DipLossHeadDesc(C.Structure):
                 ("out", C.c_void_p), ("partials", C.c_void_p), ("nblk", C.c_int32), ("loss", C.c_void_p)]
 
 
+class DipFitMonitorDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("noisy", C.c_void_p), ("gt", C.c_void_p), ("out_avg", C.c_void_p), ("n", C.c_int64),
+                ("exp_weight", C.c_float), ("backtrack_db", C.c_float), ("loss", C.c_void_p), ("partial", C.c_void_p),
+                ("records", C.c_void_p), ("capacity", C.c_int32), ("show_every", C.c_int32), ("backtracking", C.c_int32),
+                ("reserved", C.c_int32), ("counter", C.c_void_p), ("state", C.c_void_p)]
+
+
 _SIGS = {
     "dip_abi_version": (C.c_int, []),
     "dip_build_id": (C.c_char_p, []),
@@ -241,6 +248,7 @@ _SIGS = {
     "dip_fit_monitor_nblk": (C.c_int, [C.c_int64]),
     "dip_fit_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "dip_fit_monitor_dev": (C.c_int, [C.POINTER(DipFitMonitorDesc), C.c_void_p]),
     "dip_arena_backtrack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),

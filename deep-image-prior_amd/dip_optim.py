@@ -16,6 +16,7 @@ captures ONE launch list that serves all of them (every kernel launch covers all
 `NativeIteration` is the eager form without autograd: head (utils.loss_head.MSEHead), reg-noise (utils.reg_noise.RegNoise) and
 optimiser known statically, the whole iteration -- noise, forward list, loss head, backward list, Adam -- is ONE call into
 the library (dip_iter_run), bit-identical to {zero_grad(); closure(); step()} and interchangeable with it at any iteration.
+With monitor=utils.fit_monitor.FitMonitor(...) the same call also does the closure's bookkeeping (EMA, PSNRs, back-tracking).
 """
 from __future__ import annotations
 
@@ -317,10 +318,29 @@ class NativeIteration:
     The command arrays are built once and rebuilt when the engine re-plans (input size, re-typed net), when the optimiser's
     parameters move or lr / betas / eps change, and when the head's target / mask or the noise settings are replaced.  Every
     slot of them is iteration-invariant; the ONE value that changes per iteration -- where the loss scalar goes -- is a field
-    of the loss-head descriptor this object owns, which the library reads when it launches."""
+    of the loss-head descriptor this object owns, which the library reads when it launches.
 
-    def __init__(self, net, head, optimizer, net_input, reg_noise=None):
+    monitor=FitMonitor(...) adds the rest of the denoising / restoration closure (denoising.ipynb:214-248, restoration.ipynb:192-211:
+    the exponential average of the output, the three PSNRs, the back-tracking checkpoint and fall-back) to the same call: one
+    more command array on the main stream between the backward list and Adam -- where `monitor.update(out, loss)` stands in the
+    eager closure, after backward() and before opt.step() -- holding dip_fit_monitor_dev and, for a back-tracking monitor,
+    dip_arena_backtrack.  dip_fit_monitor_dev reads the iteration index from `monitor.counter` in device memory (first =
+    (i == 0), check = i % show_every != 0, record row i) and advances it, so its slots are iteration-invariant too; the loss
+    address goes into its descriptor next to the head's.  Bit-identical to the eager closure with monitor.update(), and the
+    two may alternate on one monitor: when `monitor.i` is not what the device counter will hold, the counter is set on the
+    current stream before the iteration is issued.
+
+        monitor = FitMonitor(net, img_noisy, img_gt, exp_weight=0.99, show_every=100, capacity=num_iter)
+        it = NativeIteration(net, head, opt, net_input, reg_noise=reg, monitor=monitor)
+        it.run(show_every); print(monitor.last())     # the notebook's print loop
+        monitor.history(); monitor.out_avg
+
+    step() / run(n) past the monitor's capacity raise before anything is issued.  The monitor's buffers and settings are
+    part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt)."""
+
+    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None):
         import dip_group
+        from utils.fit_monitor import FitMonitor
         from utils.loss_head import MSEHead
         from utils.reg_noise import RegNoise
         if isinstance(net, dip_group.GroupedFits) or isinstance(head, dip_group.GroupedFits):
@@ -340,6 +360,8 @@ class NativeIteration:
         if len(optimizer.params) != len(want) or any(a is not b for a, b in zip(optimizer.params, want)):
             raise ValueError("dip-amd: NativeIteration steps exactly the net's parameters (get_params('net', ...)); "
                              "opt_over with 'input' or 'down' goes through the eager closure")
+        if monitor is not None and not isinstance(monitor, FitMonitor):
+            raise TypeError(f"dip-amd: monitor must be a utils.fit_monitor.FitMonitor or None, got {type(monitor).__name__}")
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
                                "fallback)")
@@ -362,6 +384,8 @@ class NativeIteration:
         self.net, self.head, self.opt, self.engine = net, head, optimizer, eng
         self.net_input, self.reg = net_input.detach(), reg_noise
         self.device = net_input.device
+        self.monitor = monitor
+        self._check_monitor()
         self.out = None
         self.iterations = 0
         self._key = None
@@ -374,21 +398,38 @@ class NativeIteration:
             raise RuntimeError("dip-amd: NativeIteration.step() cannot be captured into a hipGraph (its loss slot changes per "
                                "iteration); capture the eager closure with GraphedIteration instead")
 
+    def _check_monitor(self):
+        """What can be said about `monitor` before the output size is known (the image shape: _build)."""
+        from utils.fit_monitor import FitMonitor
+        m = self.monitor
+        if m is None:
+            return
+        if not isinstance(m, FitMonitor):
+            raise TypeError(f"dip-amd: monitor must be a utils.fit_monitor.FitMonitor or None, got {type(m).__name__}")
+        if m.dev != self.device:
+            raise RuntimeError(f"dip-amd: the FitMonitor lives on {m.dev}, the iteration runs on {self.device}")
+        if m.engine is not None and m.engine is not self.engine:
+            raise ValueError("dip-amd: the FitMonitor back-tracks another net (it was built for a different skip() net)")
+
     # -------------------------------------------------------------------------------------------- the command arrays
     def _signature(self, sig):
         """Everything a slot of the command arrays was computed from.  Objects by identity: the arrays hold raw pointers, and
         the plan keeps every object of its key alive, so neither an id nor an address can be recycled unnoticed."""
-        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
+        eng, head, opt, reg, m = self.engine, self.head, self.opt, self.reg, self.monitor
         # (an engine that has never planned has no op lists yet: None never equals a built key)
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
                 opt.lr, opt.betas, opt.eps, id(opt._groups),
                 id(head.target), head.target.data_ptr(), id(head.mask), head.mask_c,
-                None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset)))
+                None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
+            + (() if m is None else ((id(m), id(m.records), id(m.state), id(m.out_avg), id(m.partial), id(m.snapshot),
+                                      id(m.counter), m.exp_weight, m.show_every, m.backtrack_db, id(m.noisy), id(m.gt),
+                                      id(m.engine), m.capacity, m.n),))          # (monitor=None: the key as it was)
 
     def _build(self):
-        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
+        eng, head, opt, reg, m = self.engine, self.head, self.opt, self.reg, self.monitor
         lib = N.lib()
         dev = self.device
+        self._check_monitor()
         noisy = reg is not None and reg.std > 0
         x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
         _, Cimg, H, W = x.shape
@@ -405,6 +446,8 @@ class NativeIteration:
         out = self.out
         if out is None or tuple(out.shape) != (1, eng.n_out, eng.Hout, eng.Wout) or out.device != dev:
             out = torch.empty((1, eng.n_out, eng.Hout, eng.Wout), dtype=torch.float32, device=dev)
+        if m is not None and tuple(m.noisy.shape) != tuple(out.shape):
+            raise ValueError(f"dip-amd: the FitMonitor's image is {tuple(m.noisy.shape)}, the net output is {tuple(out.shape)}")
         loss0 = torch.zeros((), dtype=torch.float32, device=dev)
         desc = head._descriptor(eng, out, loss0)
         pre = []
@@ -428,24 +471,46 @@ class NativeIteration:
             adam.append((lib.dip_adam_step_dev, (g.base, gbase + (g.base - pbase), g.m.data_ptr(), g.v.data_ptr(), g.numel,
                                                  b1, b2, float(opt.eps), st.data_ptr()), "adam_step_dev"))
         on_main = lambda ops: N.CmdList([("launch", fn, args, 0, name) for fn, args, name in ops])
-        lists = N.IterList([on_main(pre), fwd, on_main(mid), bwd, on_main(adam)])
+        phases = [on_main(pre), fwd, on_main(mid), bwd, on_main(adam)]
+        mdesc = None
+        if m is not None:
+            # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the
+            # parameters after this iteration's gradients were computed and before Adam applies them
+            mdesc = m._dev_descriptor(out)
+            mdesc.loss = loss0.data_ptr()
+            mon = [(lib.dip_fit_monitor_dev, (C.byref(mdesc),), "fit_monitor_dev")]
+            if m.engine is not None:
+                snap = m._ensure_snapshot()
+                mon.append((lib.dip_arena_backtrack, (eng.params.data_ptr(), snap.data_ptr(), eng.params.numel(),
+                                                      m.state.data_ptr()), "arena_backtrack"))
+            phases.insert(4, on_main(mon))
+        lists = N.IterList(phases)
         views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]
         self.out = out
         # everything a slot points to stays alive with the plan, and so does every object whose id is part of the key
-        self._plan = dict(lists=lists, desc=desc, views=views, x=x, state=st, loss0=loss0, scratch=head._scratch,
+        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, views=views, x=x, state=st, loss0=loss0, scratch=head._scratch,
                           keep=(head.target, head.mask, head._keep, eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
-                                None if reg is None else (reg.saved, reg.out, reg.offset)))
+                                None if reg is None else (reg.saved, reg.out, reg.offset),
+                                None if m is None else (m, m.records, m.state, m.out_avg, m.partial, m.snapshot, m.counter,
+                                                        m.noisy, m.gt, m.engine)))
         self._key = self._signature(opt._sig)
 
     # -------------------------------------------------------------------------------------------- run
-    def _begin(self):
+    def _begin(self, n=1):
         if not self.net.training:
             raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
         self._check_capture()
+        self._check_monitor()                     # (`it.monitor` may have been replaced)
+        m = self.monitor
+        if m is not None and m.i + n > m.capacity:
+            raise RuntimeError(f"dip-amd: FitMonitor capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
+                               "construct it with capacity >= num_iter")
         # (the parameters' addresses are part of the key: they also say that the engine's arena still holds the parameters)
         if self._signature(self.opt._signature()) != self._key:
             self._build()
+        if m is not None:
+            m._sync_counter()                     # eager update() calls in between: the device index follows monitor.i
         eng = self.engine
         ptrs = [torch.cuda.current_stream(self.device).cuda_stream]
         if eng.two_streams:
@@ -454,6 +519,8 @@ class NativeIteration:
 
     def _issue(self, loss_ptr, ptrs):
         self._plan["desc"].loss = loss_ptr        # read by dip_loss_head_fwd when it launches
+        if self._plan["mdesc"] is not None:
+            self._plan["mdesc"].loss = loss_ptr   # column 0 of this iteration's record (read by dip_fit_monitor_dev)
         self._plan["lists"].run(ptrs)
 
     def _finish(self, n):
@@ -465,6 +532,8 @@ class NativeIteration:
         eng.last_out, eng.last_head = self.out, self.head
         self.opt.step_count += n
         self.iterations += n
+        if self.monitor is not None:
+            self.monitor._advance(n)
 
     @torch.no_grad()
     def step(self):
@@ -484,7 +553,7 @@ class NativeIteration:
             losses = torch.empty(n, dtype=torch.float32, device=self.device)
             if n == 0:
                 return losses
-            ptrs = self._begin()
+            ptrs = self._begin(n)
             base = losses.data_ptr()
             done = 0
             try:

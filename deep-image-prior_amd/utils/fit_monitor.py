@@ -13,6 +13,15 @@ restoration.ipynb:192-211).
     hist = monitor.history()                     # [iters, 8] numpy, ONE device->host copy
     out_avg = monitor.out_avg                    # the smoothed output (1 x C x H x W, on the GPU)
 
+The same bookkeeping inside the autograd-free iteration (no Python between the iterations):
+
+    it = NativeIteration(net, head, opt, net_input, reg_noise=reg, monitor=monitor)
+    it.run(show_every); print(monitor.last())    # the notebook's print loop
+    it.run(n); hist = monitor.history()
+
+There the iteration index is read from device memory (`monitor.counter`, dip_fit_monitor_dev); `monitor.i` stays the host's
+count, and the two forms may alternate on one monitor at any iteration boundary.
+
 Record columns: loss, mse_noisy, mse_gt, mse_gt_sm, psrn_noisy, psrn_gt, psrn_gt_sm, fell_back.
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
@@ -46,6 +55,10 @@ class FitMonitor:
         self.partial = torch.empty(4 * self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float32, device=self.dev)
         self.out_avg = torch.zeros_like(self.noisy)
         self.i = 0
+        # the iteration index as dip_fit_monitor_dev reads it (NativeIteration(monitor=)), and the value it will hold once
+        # all issued work has run; update() passes `i` by value and leaves both alone, NativeIteration re-aligns them
+        self.counter = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._counter_host = 0
         self.engine = None
         self.snapshot = None
         if backtracking:
@@ -87,6 +100,35 @@ class FitMonitor:
                                                      self.state.data_ptr(), stream), "arena_backtrack")
         self._keep = o
         self.i += 1
+
+    # ------------------------------------------------------------------ the device-indexed form (dip_optim.NativeIteration)
+    def _ensure_snapshot(self):
+        """The snapshot arena, by update()'s shape rule (None without back-tracking)."""
+        if self.engine is None:
+            return None
+        params = self.engine.params
+        if self.snapshot is None or self.snapshot.numel() != params.numel() or self.snapshot.device != params.device:
+            self.snapshot = torch.empty_like(params)
+        return self.snapshot
+
+    def _dev_descriptor(self, out):
+        """DipFitMonitorDesc over this monitor's buffers for the output buffer `out`; `loss` is filled in per iteration."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return N.DipFitMonitorDesc(ptr(out), ptr(self.noisy), ptr(self.gt), ptr(self.out_avg), self.n, self.exp_weight,
+                                   self.backtrack_db, None, ptr(self.partial), ptr(self.records), self.capacity,
+                                   self.show_every, 1 if self.engine is not None else 0, 0, ptr(self.counter), ptr(self.state))
+
+    def _sync_counter(self):
+        """Sets the device counter to `i` on the current stream when it would not hold it (update() calls since the last
+        native iteration, or an `i` set by hand)."""
+        if self._counter_host != self.i:
+            self.counter.fill_(self.i)
+            self._counter_host = self.i
+
+    def _advance(self, n):
+        """n iterations were issued through dip_fit_monitor_dev."""
+        self.i += n
+        self._counter_host += n
 
     def history(self):
         """All records so far as a [iters, 8] float32 numpy array (synchronises once)."""

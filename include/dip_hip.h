@@ -640,6 +640,36 @@ int dip_fit_monitor_nblk(int64_t n);
 int dip_fit_monitor(const float* out, const float* noisy, const float* gt, float* out_avg, int64_t n,
                     float exp_weight, int first, const float* loss, float* partial, float* record,
                     float* state, int check_backtrack, float backtrack_db, void* stream);
+/* dip_fit_monitor with the iteration index in DEVICE memory: the same bookkeeping of the reference closure
+ * (denoising.ipynb:214-248; restoration.ipynb:192-211) in a form whose launch arguments do not change from one iteration
+ * to the next, so it can be a command of dip_iter_run's lists (a descriptor pointer plus the stream, like
+ * dip_loss_head_fwd).  With i = counter[0]:
+ *   first           = (i == 0)                                 (:214 `if out_avg is None`)
+ *   check_backtrack = backtracking && (i % show_every != 0)    (:238 `if i % show_every:`)
+ *   record          = records + 8*i
+ * and, after the record and `state` are written exactly as dip_fit_monitor writes them, counter[0] <- i + 1.
+ * i outside [0, capacity): records, out_avg and counter are left alone and state[1] = state[3] = 0, so the
+ * dip_arena_backtrack behind it does nothing (a guard against out-of-bounds writes; callers check the capacity first).
+ * The descriptor is read when the call launches: `loss` (this iteration's loss scalar, or NULL) may be rewritten by the
+ * host between calls.  gt may be NULL; every other pointer is required; n, capacity, show_every > 0, otherwise -1 before
+ * anything is launched.  sizeof(DipFitMonitorDesc) == 104 (LP64). */
+typedef struct DipFitMonitorDesc {
+    const float* out;       /* [n] the network output of this iteration */
+    const float* noisy;     /* [n] */
+    const float* gt;        /* [n] or NULL */
+    float* out_avg;         /* [n] */
+    int64_t n;
+    float exp_weight, backtrack_db;
+    const float* loss;      /* 1 float or NULL: column 0 of the record */
+    float* partial;         /* 4*dip_fit_monitor_nblk(n) floats of scratch */
+    float* records;         /* [capacity][8] */
+    int capacity, show_every;
+    int backtracking;       /* 0 / 1 */
+    int reserved;
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    float* state;           /* float[4], as for dip_fit_monitor */
+} DipFitMonitorDesc;
+int dip_fit_monitor_dev(const DipFitMonitorDesc* d, void* stream);
 /* applies the decision in `state` to the flat parameter arena: restore -> params = snapshot,
  * snapshot -> snapshot = params, neither -> nothing (the notebook's net_param.data.copy_(...) /
  * last_net = [x.detach().cpu() ...], :242-247) */

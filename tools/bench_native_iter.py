@@ -5,6 +5,11 @@
 for bench.py's `default` (512 x 512, reg-noise 1/30) and `library` (448 x 704, masked MSE) configurations.
 
     python tools/bench_native_iter.py [--configs default library] [--blocks 5] [--iters 50] [--out profiles/NAME.json]
+    python tools/bench_native_iter.py --monitor          # the denoising closure: + FitMonitor (EMA, 3 PSNRs, back-tracking)
+
+With --monitor both forms carry a utils.fit_monitor.FitMonitor with ground truth and back-tracking on (denoising.ipynb:204-248):
+the eager closure calls monitor.update(out, loss) between backward() and opt.step(), the other form is
+NativeIteration(monitor=); `default` only unless --configs says otherwise, result in profiles/native_iter_monitor_bench.json.
 
 Per configuration two nets are built from one seed; blocks of `--iters` iterations alternate between the two forms (A B A B
 ..., `--blocks` of each) in ONE process on one card.  Per block and iteration:
@@ -33,13 +38,14 @@ def _stats(v):
             "blocks": [round(x, 4) for x in v]}
 
 
-def child(config, blocks, iters, warmup, out_path):
+def child(config, blocks, iters, warmup, out_path, monitor=False):
     import torch          # before the library: libdip_hip.so must bind to the HIP runtime torch has loaded
     ge.build()
     import bench
     import dip_native
     from dip_optim import FusedAdam, NativeIteration
     from utils.common_utils import get_params
+    from utils.fit_monitor import FitMonitor
     from utils.loss_head import MSEHead
     from utils.reg_noise import RegNoise
     assert torch.cuda.is_available(), "bench_native_iter.py needs an MI355X"
@@ -60,20 +66,28 @@ def child(config, blocks, iters, warmup, out_path):
         head = MSEHead(net, target, mask)
         reg = RegNoise(z, reg_std, seed=1234) if reg_std > 0 else None
         opt = FusedAdam(get_params('net', net, z), lr=0.01)
-        return net, z, head, reg, opt
+        mon = None
+        if monitor:           # the notebook's settings (denoising.ipynb:136-137); room for every iteration of this run
+            g = torch.Generator().manual_seed(2000)
+            gt = torch.rand(target.shape, generator=g).to(dev)
+            mon = FitMonitor(net, target, gt, exp_weight=0.99, show_every=100, backtrack_db=5.0,
+                             capacity=warmup + blocks * iters)
+        return net, z, head, reg, opt, mon
 
-    net_a, z_a, head_a, reg_a, opt_a = make()
-    net_b, z_b, head_b, reg_b, opt_b = make()
+    net_a, z_a, head_a, reg_a, opt_a, mon_a = make()
+    net_b, z_b, head_b, reg_b, opt_b, mon_b = make()
     last = {}
 
     def eager():
         opt_a.zero_grad()
         loss, out = head_a(reg_a() if reg_a is not None else z_a)
         loss.backward()
+        if mon_a is not None:
+            mon_a.update(out, loss)
         opt_a.step()
         last["out"] = out
 
-    it = NativeIteration(net_b, head_b, opt_b, z_b, reg_noise=reg_b)
+    it = NativeIteration(net_b, head_b, opt_b, z_b, reg_noise=reg_b, monitor=mon_b)
     for _ in range(warmup):
         eager()
         it.step()
@@ -91,6 +105,9 @@ def child(config, blocks, iters, warmup, out_path):
             res[name]["host"].append((t1 - t0) / iters * 1e3)
             res[name]["wall"].append((t2 - t0) / iters * 1e3)
     same = all(torch.equal(p, q) for p, q in zip(net_a.parameters(), net_b.parameters())) and torch.equal(last["out"], it.out)
+    if monitor:
+        same = same and mon_a.i == mon_b.i and torch.equal(mon_a.records, mon_b.records) \
+            and torch.equal(mon_a.out_avg, mon_b.out_avg) and torch.equal(mon_a.state, mon_b.state)
     eng = net_b.__dict__["_dip_engine"]
     rec = {
         "config": config, "size": list(size), "blocks": blocks, "iters_per_block": iters, "warmup": warmup,
@@ -99,6 +116,9 @@ def child(config, blocks, iters, warmup, out_path):
         "eager_ms": {"wall": _stats(res["eager"]["wall"]), "host_issue": _stats(res["eager"]["host"])},
         "native_ms": {"wall": _stats(res["native"]["wall"]), "host_issue": _stats(res["native"]["host"])},
         "bit_identical_after_run": bool(same),
+        **({"monitor": {"gt": True, "backtracking": True, "show_every": mon_b.show_every, "exp_weight": mon_b.exp_weight,
+                        "iterations_recorded": mon_b.i, "fell_back": int(mon_b.history()[:, 7].sum()),
+                        "last": mon_b.last()}} if monitor else {}),
         "device": torch.cuda.get_device_name(0), "build_id": dip_native.lib().dip_build_id().decode(),
     }
     e, n = rec["eager_ms"], rec["native_ms"]
@@ -114,23 +134,28 @@ def child(config, blocks, iters, warmup, out_path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", nargs="+", default=["default", "library"], choices=["default", "library"])
+    ap.add_argument("--configs", nargs="+", default=None, choices=["default", "library"])
+    ap.add_argument("--monitor", action="store_true", help="both forms with a FitMonitor (ground truth, back-tracking)")
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per configuration")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "native_iter_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.configs is None:
+        args.configs = ["default"] if args.monitor else ["default", "library"]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "native_iter_monitor_bench.json" if args.monitor else "native_iter_bench.json")
     if args.blocks < 5 or args.iters < 50:
         ap.error("at least 5 blocks of at least 50 iterations")
     if args.child is not None:
-        child(args.child, args.blocks, args.iters, args.warmup, args.out)
+        child(args.child, args.blocks, args.iters, args.warmup, args.out, args.monitor)
         return
     parts = {c: f"{args.out}.{c}.part" for c in args.configs}
     steps = [" ".join(["timeout", "-k", "10", str(args.timeout), shlex.quote(sys.executable), shlex.quote(os.path.abspath(__file__)),
                        "--child", c, "--blocks", str(args.blocks), "--iters", str(args.iters), "--warmup", str(args.warmup),
-                       "--out", shlex.quote(p)]) for c, p in parts.items()]
+                       "--out", shlex.quote(p)] + (["--monitor"] if args.monitor else [])) for c, p in parts.items()]
     rc = subprocess.run(["bash", "-c", " && ".join(steps)]).returncode          # a failing step ends the chain
     done = {}
     for c, p in parts.items():
@@ -140,7 +165,7 @@ def main():
             os.remove(p)
     if done:
         with open(args.out, "w") as f:
-            json.dump({"tool": "tools/bench_native_iter.py", "results": done}, f, indent=1)
+            json.dump({"tool": "tools/bench_native_iter.py" + (" --monitor" if args.monitor else ""), "results": done}, f, indent=1)
             f.write("\n")
     if rc:
         raise SystemExit(f"a configuration failed (exit status {rc}); results so far: {sorted(done)}")
