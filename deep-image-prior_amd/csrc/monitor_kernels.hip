@@ -15,11 +15,26 @@
 
 namespace {
 
+// One body per phase, in two instantiations (as adam_kernel<DEV> in misc_kernels.hip).
+// DEV = false (dip_fit_monitor): `first`, `check` and the record row come from the host, by value; no counter is read or written.
+// DEV = true (dip_fit_monitor_dev): the iteration index i is counter[0], so the launch arguments are the same in every
+// iteration (a slot of NativeIteration's command arrays must be iteration-invariant): first = (i == 0), check = backtracking &&
+// i % show_every != 0, the row is records + 8 * i, and the finalize kernel's last store is counter[0] = i + 1.  i outside
+// [0, capacity) is the overflow guard: nothing is written to records / out_avg / counter and the decision flags are cleared,
+// so the arena_backtrack launch that follows does nothing.
+template <bool DEV>
 __global__ __launch_bounds__(256) void fit_monitor_partials_kernel(const float* __restrict__ out,
                                                                    const float* __restrict__ noisy,
                                                                    const float* __restrict__ gt, float* __restrict__ avg,
-                                                                   int64_t n, float w, int first, float* __restrict__ partial) {
+                                                                   int64_t n, float w, int first,
+                                                                   const int* __restrict__ counter, int capacity,
+                                                                   float* __restrict__ partial) {
     __shared__ float sh[3][256];
+    if constexpr (DEV) {
+        const int it = counter[0];                // uniform; the finalize launch behind this one advances it
+        if (it < 0 || it >= capacity) return;
+        first = it == 0;
+    }
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float o = out[i];
@@ -50,11 +65,26 @@ __global__ __launch_bounds__(256) void fit_monitor_partials_kernel(const float* 
 
 // record: [loss, mse_noisy, mse_gt, mse_gt_sm, psnr_noisy, psnr_gt, psnr_gt_sm, fell_back]
 // state:  [psnr_noisy_last, restore_flag, have_last, snapshot_flag]
+// DEV = false: `record` is the row and `check` the host's decision; DEV = true: `record` is row 0 of the table and `check`
+// says whether the monitor back-tracks at all.
+template <bool DEV>
 __global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* __restrict__ partial, int nblk, int64_t n,
                                                                   int have_gt, const float* __restrict__ loss,
                                                                   float* __restrict__ record, float* __restrict__ state,
-                                                                  int check, float thresh_db) {
+                                                                  int check, float thresh_db, int* __restrict__ counter,
+                                                                  int capacity, int show_every) {
     if (threadIdx.x != 0) return;
+    int it = 0;
+    if constexpr (DEV) {
+        it = counter[0];
+        if (it < 0 || it >= capacity) {           // guard: the host refuses first (FitMonitor / NativeIteration)
+            state[1] = 0.f;
+            state[3] = 0.f;
+            return;
+        }
+        record += 8 * (int64_t)it;
+        check = check && (it % show_every != 0);
+    }
     double s[3] = {0.0, 0.0, 0.0};
     for (int b = 0; b < nblk; ++b)
         for (int k = 0; k < 3; ++k) s[k] += (double)partial[b * 4 + k];
@@ -79,89 +109,7 @@ __global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* _
     state[1] = restore;
     state[3] = snap;
     record[7] = restore;
-}
-
-// Device-indexed forms (dip_fit_monitor_dev): the iteration index i comes from counter[0] instead of the host, so the launch
-// arguments are the same in every iteration (a slot of NativeIteration's command arrays must be iteration-invariant).  The
-// arithmetic is the two kernels above, statement for statement: same grid, same LDS pairing order, same fixed-order fp64 sum.
-// i outside [0, capacity) is the overflow guard: nothing is written to records / out_avg / counter and the decision flags are
-// cleared, so the arena_backtrack launch that follows does nothing.
-__global__ __launch_bounds__(256) void fit_monitor_partials_dev_kernel(const float* __restrict__ out,
-                                                                       const float* __restrict__ noisy,
-                                                                       const float* __restrict__ gt, float* __restrict__ avg,
-                                                                       int64_t n, float w, const int* __restrict__ counter,
-                                                                       int capacity, float* __restrict__ partial) {
-    __shared__ float sh[3][256];
-    const int it = counter[0];                    // uniform; the finalize launch behind this one advances it
-    if (it < 0 || it >= capacity) return;
-    const int first = it == 0;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float o = out[i];
-        const float a = first ? o : fmaf(avg[i], w, o * (1.f - w));
-        avg[i] = a;
-        const float dn = o - noisy[i];
-        s0 = fmaf(dn, dn, s0);
-        if (gt != nullptr) {
-            const float g = gt[i];
-            s1 = fmaf(o - g, o - g, s1);
-            s2 = fmaf(a - g, a - g, s2);
-        }
-    }
-    sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1; sh[2][threadIdx.x] = s2;
-    for (int s = 128; s >= 1; s >>= 1) {          // fixed pairing order: deterministic
-        __syncthreads();
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
-        }
-    }
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 4 + 0] = sh[0][0];
-        partial[blockIdx.x * 4 + 1] = sh[1][0];
-        partial[blockIdx.x * 4 + 2] = sh[2][0];
-    }
-}
-
-__global__ __launch_bounds__(64) void fit_monitor_finalize_dev_kernel(const float* __restrict__ partial, int nblk, int64_t n,
-                                                                      int have_gt, const float* __restrict__ loss,
-                                                                      float* __restrict__ records, int capacity,
-                                                                      float* __restrict__ state, int* __restrict__ counter,
-                                                                      int show_every, int backtracking, float thresh_db) {
-    if (threadIdx.x != 0) return;
-    const int it = counter[0];
-    if (it < 0 || it >= capacity) {               // guard: the host refuses first (FitMonitor / NativeIteration)
-        state[1] = 0.f;
-        state[3] = 0.f;
-        return;
-    }
-    float* record = records + 8 * (int64_t)it;
-    const int check = backtracking && (it % show_every != 0);
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int b = 0; b < nblk; ++b)
-        for (int k = 0; k < 3; ++k) s[k] += (double)partial[b * 4 + k];
-    float mse[3], psnr[3];
-    for (int k = 0; k < 3; ++k) {
-        mse[k] = (float)(s[k] / (double)n);
-        psnr[k] = (float)(-10.0 * log10(s[k] / (double)n));      // data_range = 1
-    }
-    record[0] = loss != nullptr ? loss[0] : 0.f;
-    record[1] = mse[0]; record[2] = have_gt ? mse[1] : 0.f; record[3] = have_gt ? mse[2] : 0.f;
-    record[4] = psnr[0]; record[5] = have_gt ? psnr[1] : 0.f; record[6] = have_gt ? psnr[2] : 0.f;
-    float restore = 0.f, snap = 0.f;
-    if (check) {
-        if (state[2] != 0.f && psnr[0] - state[0] < -thresh_db) {
-            restore = 1.f;                                        // "Falling back to previous checkpoint."
-        } else {
-            snap = 1.f;
-            state[0] = psnr[0];
-            state[2] = 1.f;
-        }
-    }
-    state[1] = restore;
-    state[3] = snap;
-    record[7] = restore;
-    counter[0] = it + 1;
+    if constexpr (DEV) counter[0] = it + 1;
 }
 
 __global__ __launch_bounds__(256) void arena_backtrack_kernel(float* __restrict__ params, float* __restrict__ snapshot,
@@ -196,11 +144,11 @@ extern "C" int dip_fit_monitor(const float* out, const float* noisy, const float
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (n <= 0 || out == nullptr || noisy == nullptr || out_avg == nullptr) DIP_FAIL("fit_monitor: bad arguments");
     const int nblk = dip_fit_monitor_nblk(n);
-    dip_launch(fit_monitor_partials_kernel, dim3(nblk), dim3(256), 0, st, out, noisy, gt, out_avg, n, exp_weight,
-                       first, partial);
+    dip_launch(fit_monitor_partials_kernel<false>, dim3(nblk), dim3(256), 0, st, out, noisy, gt, out_avg, n, exp_weight,
+               first, (const int*)nullptr, 0, partial);
     DIP_CHECK_LAUNCH();
-    dip_launch(fit_monitor_finalize_kernel, dim3(1), dim3(64), 0, st, partial, nblk, n, gt != nullptr ? 1 : 0,
-                       loss, record, state, check_backtrack, backtrack_db);
+    dip_launch(fit_monitor_finalize_kernel<false>, dim3(1), dim3(64), 0, st, (const float*)partial, nblk, n,
+               gt != nullptr ? 1 : 0, loss, record, state, check_backtrack, backtrack_db, (int*)nullptr, 0, 0);
     DIP_CHECK_LAUNCH();
     return 0;
 }
@@ -213,12 +161,12 @@ extern "C" int dip_fit_monitor_dev(const DipFitMonitorDesc* d, void* stream) {
         DIP_FAIL("fit_monitor_dev: a required pointer is NULL");
     if (d->n <= 0 || d->capacity <= 0 || d->show_every <= 0) DIP_FAIL("fit_monitor_dev: n, capacity and show_every must be > 0");
     const int nblk = dip_fit_monitor_nblk(d->n);
-    dip_launch(fit_monitor_partials_dev_kernel, dim3(nblk), dim3(256), 0, st, d->out, d->noisy, d->gt, d->out_avg, d->n,
-               d->exp_weight, (const int*)d->counter, d->capacity, d->partial);
+    dip_launch(fit_monitor_partials_kernel<true>, dim3(nblk), dim3(256), 0, st, d->out, d->noisy, d->gt, d->out_avg, d->n,
+               d->exp_weight, 0, (const int*)d->counter, d->capacity, d->partial);
     DIP_CHECK_LAUNCH();
-    dip_launch(fit_monitor_finalize_dev_kernel, dim3(1), dim3(64), 0, st, (const float*)d->partial, nblk, d->n,
-               d->gt != nullptr ? 1 : 0, d->loss, d->records, d->capacity, d->state, d->counter, d->show_every,
-               d->backtracking != 0 ? 1 : 0, d->backtrack_db);
+    dip_launch(fit_monitor_finalize_kernel<true>, dim3(1), dim3(64), 0, st, (const float*)d->partial, nblk, d->n,
+               d->gt != nullptr ? 1 : 0, d->loss, d->records, d->state, d->backtracking != 0 ? 1 : 0, d->backtrack_db,
+               d->counter, d->capacity, d->show_every);
     DIP_CHECK_LAUNCH();
     return 0;
 }

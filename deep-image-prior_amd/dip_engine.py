@@ -121,7 +121,7 @@ class SkipEngine:
         self.fwd_id = 0
         self._aux = {}                 # (capture | eager, device) -> ([side stream, bulk stream], events)
         self.two_streams = os.environ.get("DIP_TWO_STREAMS", "1") != "0"
-        # backward schedule (see _run_two_streams): the weight gradients emitted before the backward walk reaches
+        # backward schedule (see _issue): the weight gradients emitted before the backward walk reaches
         # scale `defer_scale` are held back until then, later ones until the end of their scale's decoder / encoder
         # part (-1: every one is launched where it is emitted)
         self.defer_scale = int(os.environ.get("DIP_DEFER_WGRAD", "2")) if self.two_streams else -1
@@ -572,7 +572,7 @@ class SkipEngine:
             plan = N.conv_plan if bf3_ok else N.conv_plan_fp32
             ksplit, ntiles, wsf = plan(Ho, Wo, round_up(x.C, 4), r.Cout, r.ks, r.stride)
         # the skip-branch convs run on the side stream next to the encoder convs of their scale
-        # (_run_two_streams), so they get scratch of their own
+        # (_issue), so they get scratch of their own
         # (a skip conv below DIP_SIDE_MIN_PIXELS stays on the main stream AND on the main stream's scratch: the side
         # stream may still be running the previous scale's skip conv out of scratch set 2 -- round-3 advisor finding)
         side = r.name.endswith("skip_conv") and Ho * Wo >= self.side_min_pixels and bn is not None
@@ -1094,9 +1094,13 @@ class SkipEngine:
             st_ = self._aux[(slot, self.device)] = ([torch.cuda.Stream(self.device) for _ in range(3)], {})
         return slot, st_[0], st_[1]
 
-    def _issue(self, ops, main, key, cls_fn=None, join_before_fn=None, deps=None, compile_only=False):
-        """Issues a launch list: compiled once per (key, length) into a command list and run by ONE dip_list_run call, or
-        (DIP_NO_CLIST=1) walked in Python with torch events -- the same schedule either way.
+    def _issue(self, ops, main, key, cls_fn=None, join_before_fn=None, deps=None, compile_only=False, drop_last=False):
+        """Issues the launch list `ops` (drop_last: all of it but its last op): compiled once into a command list and run by
+        ONE dip_list_run call, or (DIP_NO_CLIST=1) walked in Python with torch events -- the same schedule either way.
+        The cache entry of (key, drop_last) remembers the list object it was compiled from; another list under the same key is
+        compiled afresh and replaces it.  A compiled list is replayed as it is: every argument of every op must be
+        iteration-invariant (what changes per iteration lives in device memory, or in a descriptor the library reads when it
+        launches).
         compile_only: nothing is issued; returns the compiled command list (None under DIP_NO_CLIST=1)."""
         multi = cls_fn is not None
         slot, aux, events = self._aux_streams() if multi else ("one", [], None)
@@ -1104,10 +1108,11 @@ class SkipEngine:
         if self._knockout is not None:          # DIP_KNOCKOUT_AFTER=n: the first n issues of a list run whole (buffers hold real values)
             n = self._ko_seen[key] = self._ko_seen.get(key, 0) + 1
             ko = n > self._ko_after
-        ck = (key, len(ops), multi, ko)
+        ck = (key, drop_last, multi, ko)
         ent = self._clists.get(ck)
-        if ent is None:
-            sched = self._schedule(ops, cls_fn, join_before_fn, deps)
+        if ent is None or ent[0] is not ops:
+            # (the schedule's launch indices hold for `ops` itself: dropping the LAST op moves no other)
+            sched = self._schedule(ops[:-1] if drop_last else ops, cls_fn, join_before_fn, deps)
             if ko:                              # timing experiment: these launches are left out (the results are WRONG)
                 sched = [c for c in sched if not (c[0] == "launch" and self._knockout.search(ops[c[1]][2]))]
             cl = None
@@ -1123,8 +1128,8 @@ class SkipEngine:
                     else:
                         cmds.append(("wait", c[1], evidx.setdefault(c[2], len(evidx))))
                 cl = N.CmdList(cmds)
-            ent = self._clists[ck] = (sched, cl)
-        sched, cl = ent
+            ent = self._clists[ck] = (ops, sched, cl)
+        _, sched, cl = ent
         if compile_only:
             return cl
         if cl is not None:
@@ -1146,12 +1151,6 @@ class SkipEngine:
                 ev.record(streams[c[2]])
             else:
                 streams[c[1]].wait_event(events[(key, c[2])])
-
-    def _run(self, ops, main, key="one", compile_only=False):
-        return self._issue(ops, main, key, compile_only=compile_only)
-
-    def _run_two_streams(self, ops, main, cls_fn, join_before_fn, key, deps=None, compile_only=False):
-        return self._issue(ops, main, key, cls_fn, join_before_fn, deps, compile_only)
 
     # stream class of a backward op: 2 = bulk (weight gradients), 1 = side, 0 = main
     _BWD_SIDE = staticmethod(lambda n: 2 if n.startswith(("wgrad:", "wgred:")) else
@@ -1186,7 +1185,7 @@ class SkipEngine:
             consumer = next((n for n in names[j + 1:] if not self._BWD_SIDE(n)), None)
             if consumer is not None:
                 deps.setdefault(consumer, []).append(name)
-            # (no main-stream op behind it: the final join of _run_two_streams covers it)
+            # (no main-stream op behind it: the final join of _issue covers it)
         return deps
 
     def _run_backward_two_streams(self, ops, main, compile_only=False):
@@ -1200,12 +1199,12 @@ class SkipEngine:
         capturing = torch.cuda.is_current_stream_capturing()
         bulk2 = self._bulk2 if not capturing else ()
         cls = self._BWD_SIDE if not bulk2 else (lambda n: 3 if n in bulk2 else self._BWD_SIDE(n))
-        return self._run_two_streams(ops, main, cls, lambda n: False, "bwd_cap" if capturing else "bwd", deps, compile_only)
+        return self._issue(ops, main, "bwd_cap" if capturing else "bwd", cls, lambda n: False, deps, compile_only)
 
-    def _run_forward_two_streams(self, ops, main, compile_only=False):
+    def _run_forward_two_streams(self, ops, main, compile_only=False, drop_last=False):
         side = self._fwd_side
-        return self._run_two_streams(ops, main, lambda n: 1 if n in side else 0, lambda n: n.startswith("upcat:"), "fwd",
-                                     compile_only=compile_only)
+        return self._issue(ops, main, "fwd", lambda n: 1 if n in side else 0, lambda n: n.startswith("upcat:"),
+                           compile_only=compile_only, drop_last=drop_last)
 
     def _forward_prologue(self, x_ptr):
         """The launches in front of the forward list, as (fn, args, name): weight repack, NCHW -> NHWC of the input at x_ptr."""
@@ -1228,16 +1227,16 @@ class SkipEngine:
             stream = main.cuda_stream
             for fn, args, name in self._forward_prologue(x_ptr):
                 N.check(fn(*args, stream), name)
-        ops = self.fwd_ops if with_out_conv else self.fwd_ops[:-1]      # the last op is the output conv
+        drop_last = not with_out_conv          # the last op is the output conv
         if self.two_streams:
-            return self._run_forward_two_streams(ops, main, compile_only)
-        return self._run(ops, main, "fwd1", compile_only)
+            return self._run_forward_two_streams(self.fwd_ops, main, compile_only, drop_last)
+        return self._issue(self.fwd_ops, main, "fwd1", compile_only=compile_only, drop_last=drop_last)
 
     def _launch_backward(self, main, compile_only=False):
         """The static backward launch list (dy of the output conv already in self.dy_out)."""
         if self.two_streams:
             return self._run_backward_two_streams(self.bwd_ops, main, compile_only)
-        return self._run(self.bwd_ops, main, "bwd1", compile_only)
+        return self._issue(self.bwd_ops, main, "bwd1", compile_only=compile_only)
 
     def iteration_lists(self):
         """(forward list without the output conv, backward list) of the current plan as the compiled command lists an eager
@@ -1259,6 +1258,16 @@ class SkipEngine:
         """Gradient source (buf, pad) wrt the net's input, left by self.bwd_input_ops."""
         return self.sc[0].gin
 
+    def _prepare(self, dev, H, W, Cimg):
+        """Arenas on `dev` and the plan for a [1, Cimg, H, W] input: rebuilt when the device changed or the arena went stale,
+        re-planned when the shape changed."""
+        if self.device != dev or not self._arena_ok():
+            self._build_arenas(dev)
+        if self.shape_key != (H, W, Cimg):
+            if Cimg != self._net_cin():
+                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {self._net_cin()}")
+            self._build_plan(H, W, Cimg)
+
     def forward(self, x: torch.Tensor, head=None):
         """Runs the forward launch list.  head = None: returns the network output [1,C,H,W].
         head = a utils.loss_head.MSEHead: the output conv + sigmoid + (mask) + MSE run as ONE launch
@@ -1270,13 +1279,8 @@ class SkipEngine:
             raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (the reference never "
                                       "calls .eval() on the skip path)")
         dev = x.device
-        if self.device != dev or not self._arena_ok():
-            self._build_arenas(dev)
         _, Cimg, H, W = x.shape
-        if self.shape_key != (H, W, Cimg):
-            if Cimg != self._net_cin():
-                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {self._net_cin()}")
-            self._build_plan(H, W, Cimg)
+        self._prepare(dev, H, W, Cimg)
         lib = self.lib
         with torch.cuda.device(dev):          # raw HIP launches go to the CURRENT device's streams
             main = torch.cuda.current_stream(dev)
@@ -1354,7 +1358,7 @@ class SkipEngine:
             self._launch_backward(main)
             gx = None
             if need_input_grad:
-                self._run(self.bwd_input_ops, main, "bwdin")
+                self._issue(self.bwd_input_ops, main, "bwdin")
                 gbuf, pad = self._input_gin()
                 src = N.DipGradSrc(_ptr(gbuf), pad, 1 if pad > 0 else 0, round_up(self.Cimg, 4), 0)
                 gx = torch.empty((1, self.Cimg, H, W), dtype=torch.float32, device=dev)

@@ -340,7 +340,6 @@ class NativeIteration:
 
     def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None):
         import dip_group
-        from utils.fit_monitor import FitMonitor
         from utils.loss_head import MSEHead
         from utils.reg_noise import RegNoise
         if isinstance(net, dip_group.GroupedFits) or isinstance(head, dip_group.GroupedFits):
@@ -352,16 +351,17 @@ class NativeIteration:
         if eng.kind != "skip":
             raise NotImplementedError("dip-amd: NativeIteration covers skip() nets; the ResNet backbone has no fused loss head "
                                       "(run it through the eager closure)")
-        if not net.training:
-            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
+        self.net, self.engine = net, eng
+        self._check_training()
         if not isinstance(optimizer, FusedAdam):
             raise TypeError(f"dip-amd: NativeIteration needs a dip_optim.FusedAdam, got {type(optimizer).__name__}")
         want = eng.param_list
         if len(optimizer.params) != len(want) or any(a is not b for a, b in zip(optimizer.params, want)):
             raise ValueError("dip-amd: NativeIteration steps exactly the net's parameters (get_params('net', ...)); "
                              "opt_over with 'input' or 'down' goes through the eager closure")
-        if monitor is not None and not isinstance(monitor, FitMonitor):
-            raise TypeError(f"dip-amd: monitor must be a utils.fit_monitor.FitMonitor or None, got {type(monitor).__name__}")
+        # (the monitor's type is refused before the first check that needs a GPU)
+        self.monitor, self.device = monitor, getattr(net_input, "device", None)
+        self._check_monitor()
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
                                "fallback)")
@@ -381,11 +381,8 @@ class NativeIteration:
                                 f"{type(reg_noise).__name__}")
             if reg_noise.saved.shape != net_input.shape or reg_noise.saved.device != net_input.device:
                 raise ValueError("dip-amd: the RegNoise was built for another net_input")
-        self.net, self.head, self.opt, self.engine = net, head, optimizer, eng
+        self.head, self.opt = head, optimizer
         self.net_input, self.reg = net_input.detach(), reg_noise
-        self.device = net_input.device
-        self.monitor = monitor
-        self._check_monitor()
         self.out = None
         self.iterations = 0
         self._key = None
@@ -397,6 +394,10 @@ class NativeIteration:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("dip-amd: NativeIteration.step() cannot be captured into a hipGraph (its loss slot changes per "
                                "iteration); capture the eager closure with GraphedIteration instead")
+
+    def _check_training(self):
+        if not self.net.training:
+            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
 
     def _check_monitor(self):
         """What can be said about `monitor` before the output size is known (the image shape: _build)."""
@@ -433,13 +434,7 @@ class NativeIteration:
         noisy = reg is not None and reg.std > 0
         x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
         _, Cimg, H, W = x.shape
-        # the engine's own preparation, as SkipEngine.forward does it
-        if eng.device != dev or not eng._arena_ok():
-            eng._build_arenas(dev)
-        if eng.shape_key != (H, W, Cimg):
-            if Cimg != eng._net_cin():
-                raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {eng._net_cin()}")
-            eng._build_plan(H, W, Cimg)
+        eng._prepare(dev, H, W, Cimg)
         if opt._sig != opt._signature():
             opt._prepare()
         fwd, bwd = eng.iteration_lists()
@@ -498,8 +493,7 @@ class NativeIteration:
 
     # -------------------------------------------------------------------------------------------- run
     def _begin(self, n=1):
-        if not self.net.training:
-            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
+        self._check_training()
         self._check_capture()
         self._check_monitor()                     # (`it.monitor` may have been replaced)
         m = self.monitor

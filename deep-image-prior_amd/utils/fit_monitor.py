@@ -91,19 +91,17 @@ class FitMonitor:
                                              self.out_avg.data_ptr(), self.n, self.exp_weight, 1 if self.i == 0 else 0,
                                              lptr, self.partial.data_ptr(), self.records[self.i].data_ptr(),
                                              self.state.data_ptr(), check, self.backtrack_db, stream), "fit_monitor")
-            if self.engine is not None:
+            snap = self._ensure_snapshot()
+            if snap is not None:
                 params = self.engine.params
-                if self.snapshot is None or self.snapshot.numel() != params.numel() \
-                        or self.snapshot.device != params.device:
-                    self.snapshot = torch.empty_like(params)
-                N.check(self.lib.dip_arena_backtrack(params.data_ptr(), self.snapshot.data_ptr(), params.numel(),
+                N.check(self.lib.dip_arena_backtrack(params.data_ptr(), snap.data_ptr(), params.numel(),
                                                      self.state.data_ptr(), stream), "arena_backtrack")
         self._keep = o
         self.i += 1
 
     # ------------------------------------------------------------------ the device-indexed form (dip_optim.NativeIteration)
     def _ensure_snapshot(self):
-        """The snapshot arena, by update()'s shape rule (None without back-tracking)."""
+        """The snapshot arena, as large as the engine's parameter arena and on its device (None without back-tracking)."""
         if self.engine is None:
             return None
         params = self.engine.params

@@ -232,6 +232,33 @@ def test_replanning_input_size(dev):
     assert torch.equal(torch.stack(la), torch.stack(lb))
 
 
+def test_command_list_cache_is_keyed_on_the_list_it_compiled(dev):
+    """The engine's compiled lists are found again by the identity of the op list they were compiled from -- the forward list
+    without the output conv by that of fwd_ops, not of the slice -- another list under the same key is compiled afresh in
+    place of the old one, and an iteration compiles nothing."""
+    b = _tiny(dev, "default", size=(32, 48))         # (the size of tests/golden/net_tiny_default.npz)
+    it = _native(b)
+    it.step()
+    eng = b.net.__dict__["_dip_engine"]
+    fwd, bwd = eng._launch_forward(None, None, False, compile_only=True), eng._launch_backward(None, compile_only=True)
+    assert fwd is not None and bwd is not None and fwd is not bwd
+    assert eng._launch_forward(None, None, False, compile_only=True) is fwd
+    assert eng._launch_backward(None, compile_only=True) is bwd
+    lists = it._plan["lists"]
+    for _ in range(20):
+        it.step()
+    assert eng._launch_forward(None, None, False, compile_only=True) is fwd          # no recompile per iteration
+    assert eng._launch_backward(None, compile_only=True) is bwd
+    assert it._plan["lists"] is lists and it.iterations == 21
+    n = len(eng._clists)
+    eng.bwd_ops = list(eng.bwd_ops)                  # same length, same contents, another object
+    bwd2 = eng._launch_backward(None, compile_only=True)
+    assert bwd2 is not bwd and len(eng._clists) == n
+    assert eng._launch_backward(None, compile_only=True) is bwd2
+    assert eng._launch_forward(None, None, False, compile_only=True) is fwd
+    torch.cuda.synchronize()
+
+
 def test_refuses_capture_and_eval(dev, monkeypatch):
     b = _tiny(dev, "snail")
     it = _native(b)
