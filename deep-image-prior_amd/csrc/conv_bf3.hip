@@ -27,13 +27,10 @@
 #include "dip_common.h"
 #include "dip_group.h"
 #include "conv_epilogue.h"
+#include "bf3.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef DIP_W3_PROFILE
 // clock probe of the profile build (tools/w3_profile.py): per workgroup {s_memtime cycles, s_memrealtime ticks (100 MHz)} of wave 0
@@ -59,25 +56,44 @@ struct B3Cfg {
     static constexpr int LDS_BYTES = 2 * A_BYTES + NPIX_PAD * 4 + 2 * B3_TR_MAX * 4;      // 39.4 KB
 };
 
-__device__ __forceinline__ int b3_map_src(int v, int n_in, int pad_mode) {
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
-    return (v < 0 || v >= n_in) ? -1 : v;
+// ---- what the 3x3 kernel and the 1x1 kernel share (C = their B3Cfg) ----
+// the three planes of a unit's weights at ub: wave-uniform base (SGPR pair) + 32-bit per-lane offset
+template <int NS>
+__device__ __forceinline__ void b3_load_b(bf16x8 (&bs)[NS][3], const unsigned char* ub, size_t plane_bytes, const unsigned (&b_voff)[NS]) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        const unsigned long long b64 = (unsigned long long)(ub + p * plane_bytes);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b64);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b64 >> 32));
+        const void* sb = (const void*)(((unsigned long long)hi << 32) | lo);
+#pragma unroll
+        for (int ns = 0; ns < NS; ++ns)
+            asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(bs[ns][p]) : "v"(b_voff[ns]), "s"(sb));
+    }
+}
+// one staged float4 (already zeroed where it is padding, else transformed): exact split, three bf16 planes at `base`
+template <class C>
+__device__ __forceinline__ void b3_split_store(unsigned char* base, const f32x4 o) {
+    unsigned h[4], m[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dip_bf3_split(o[e], h[e], m[e], l[e]);
+    *reinterpret_cast<u32x2*>(base) = dip_bf3_pack4(h);
+    *reinterpret_cast<u32x2*>(base + C::A_PLANE) = dip_bf3_pack4(m);
+    *reinterpret_cast<u32x2*>(base + 2 * C::A_PLANE) = dip_bf3_pack4(l);
+}
+// the MFMAs of one unit: NT products x 2 pixel blocks x NS column blocks
+template <int NT, int NS>
+__device__ __forceinline__ void b3_mfma(f32x16 (&acc)[2][NS], const bf16x8 (&bs)[NS][3], const bf16x8 (&as)[2][3]) {
+    dip_bf3_products<NT>([&](auto PA, auto PB) {
+#pragma unroll
+        for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+            for (int ns = 0; ns < NS; ++ns)
+                acc[ms][ns] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[ms][decltype(PA)::value], bs[ns][decltype(PB)::value], acc[ms][ns], 0, 0, 0);
+    });
 }
 
-// exact three-way split by truncation: a == hi + mid + lo, each with <= 8 significand bits (a bf16 number)
-__device__ __forceinline__ void b3_split(float a, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned uh = __float_as_uint(a) & 0xFFFF0000u;
-    const float r1 = a - __uint_as_float(uh);
-    const unsigned um = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(um);
-    h = uh;
-    m = um;
-    l = __float_as_uint(r2) & 0xFFFF0000u;        // (<= 8 significand bits are left: the mask only drops zeros)
-}
-
-// NT = 9: all cross products (exact); NT = 8: without lo*lo (< 2^-32 of the product: 2^-8 of the rounding error of ONE fp32
-// accumulation step, so the sum is as accurate as with it); NT = 6: also without lo*mid, mid*lo (each < 2^-24 of the product).
+// NT: the number of partial products (bf3.h: dip_bf3_products).
 //
 // The B operand (weights) goes straight from L2 into registers, one unit ahead: no weight buffers in LDS, no LDS-DMA, and
 // ONE workgroup barrier per 16-channel chunk (9 units) -- the waves of a workgroup only meet where the A buffers change hands.
@@ -115,8 +131,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
 
     for (int hp = tid; hp < C::NPIX; hp += 256) {
         const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-        const int sr = b3_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
-        const int sc = b3_map_src(tx * C::TW + hc - d.off, d.Win, d.pad_mode);
+        const int sr = dip_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
+        const int sc = dip_map_src(tx * C::TW + hc - d.off, d.Win, d.pad_mode);
         srcoff[hp] = (sr < 0 || sc < 0) ? -1 : (sr * d.Win + sc);
     }
     const float slope = d.tr.slope;
@@ -144,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
 #pragma unroll
     for (int ms = 0; ms < 2; ++ms) a_pix[ms] = (2 * (wm * 2 + ms) + (l31 >> 4)) * C::HTW + (l31 & 15);
 
-    // ---- A: as in conv_bf3_kernel (halo fp32 -> registers one chunk ahead -> transform, exact split, three bf16 planes) ----
+    // ---- A: halo fp32 -> registers one chunk ahead -> transform, exact split, three bf16 planes ----
     f32x4 av[C::A_SLOTS];
 #pragma unroll
     for (int i = 0; i < C::A_SLOTS; ++i) av[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -185,21 +201,9 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
                 f32x4 o = av[i];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = valid ? o[e] : 0.f;
-                if (TR && valid) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(tra + c), b4 = *reinterpret_cast<const f32x4*>(trb + c);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float tv = fmaf(a4[e], o[e], b4[e]);
-                        o[e] = TR == 1 ? dip_act_leaky(tv, slope) : dip_act(tv, slope);
-                    }
-                }
-                unsigned h[4], m[4], l[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) b3_split(o[e], h[e], m[e], l[e]);
+                if (TR && valid) o = dip_bf3_transform<TR>(o, tra + c, trb + c, slope);
                 unsigned char* base = Abuf + buf * C::A_BYTES + hp * 32 + ((((c4 >> 1) ^ (hp >> 3)) & 1) << 4) + ((c4 & 1) << 3);
-                *reinterpret_cast<u32x2*>(base) = u32x2{(h[0] >> 16) | h[1], (h[2] >> 16) | h[3]};
-                *reinterpret_cast<u32x2*>(base + C::A_PLANE) = u32x2{(m[0] >> 16) | m[1], (m[2] >> 16) | m[3]};
-                *reinterpret_cast<u32x2*>(base + 2 * C::A_PLANE) = u32x2{(l[0] >> 16) | l[1], (l[2] >> 16) | l[3]};
+                b3_split_store<C>(base, o);
             }
         }
     };
@@ -223,18 +227,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
     const size_t plane_bytes = (size_t)CoutP * 32;
     typedef bf16x8 (&BSet)[NS][3];
     auto loadB = [&](BSet bs, int tapn, int chn) {
-        const unsigned char* ub = w3 + (size_t)(tapn * nch + chn) * 3 * plane_bytes;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            // wave-uniform base (SGPR pair) + 32-bit per-lane offset
-            const unsigned long long b64 = (unsigned long long)(ub + p * plane_bytes);
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b64);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b64 >> 32));
-            const void* sb = (const void*)(((unsigned long long)hi << 32) | lo);
-#pragma unroll
-            for (int ns = 0; ns < NS; ++ns)
-                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(bs[ns][p]) : "v"(b_voff[ns]), "s"(sb));
-        }
+        b3_load_b(bs, w3 + (size_t)(tapn * nch + chn) * 3 * plane_bytes, plane_bytes, b_voff);
     };
     // all B loads of the set have landed; keep3 (wave-uniform): the 3 halo loads issued after them may stay in flight.
     // One unconditional statement with the choice inside (see loadA).
@@ -285,22 +278,6 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
             for (int p = 0; p < 3; ++p) as[ms][p] = *reinterpret_cast<const bf16x8*>(pa + p * C::A_PLANE);
         }
     };
-    auto compute = [&](BSet bs, ASet as) {
-#pragma unroll
-        for (int sm = 4; sm >= 0; --sm) {          // smallest partial products first
-            if ((NT == 6 && sm > 2) || (NT == 8 && sm > 3)) continue;
-#pragma unroll
-            for (int pa = 0; pa < 3; ++pa) {
-                const int pb = sm - pa;
-                if (pb < 0 || pb > 2) continue;
-#pragma unroll
-                for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-                    for (int ns = 0; ns < NS; ++ns)
-                        acc[ms][ns] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[ms][pa], bs[ns][pb], acc[ms][ns], 0, 0, 0);
-            }
-        }
-    };
 
     // ---- prologue ----
     __syncthreads();                    // srcoff / tr tables
@@ -329,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_kernel(const DipConvDesc d, c
         const bool ld = tap == 0 && next_chunk;
         loadA(ch + 1, ld);                                       // AFTER this unit's B loads: they can be waited for alone
         readA(anxt, tapn, chn & 1, tail && chn == nch - 1);      // next unit's A fragments, under this unit's MFMAs
-        compute(cur, acur);
+        b3_mfma<NT>(acc, cur, acur);
         __builtin_amdgcn_sched_barrier(0);          // (hipcc hoisted the wait to the 4th MFMA: a full L2 latency exposed per unit)
         waitB(nxt, ld);
         // A buffers change hands: the stores of tap 4 become visible before tap 8 reads the next chunk's first fragments, and
@@ -393,8 +370,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_k1_kernel(const DipConvDesc d
 
     if (tid < C::NPIX) {
         const int hr = tid / C::HTW, hc = tid - hr * C::HTW;
-        const int sr = b3_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
-        const int sc = b3_map_src(tx * C::TW + hc - d.off, d.Win, d.pad_mode);
+        const int sr = dip_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
+        const int sc = dip_map_src(tx * C::TW + hc - d.off, d.Win, d.pad_mode);
         srcoff[tid] = (sr < 0 || sc < 0) ? -1 : (sr * d.Win + sc);
     }
     const float slope = d.tr.slope;
@@ -442,21 +419,9 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_k1_kernel(const DipConvDesc d
             f32x4 o = a[i];
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = valid ? o[e] : 0.f;
-            if (TR && valid) {
-                const f32x4 a4 = *reinterpret_cast<const f32x4*>(tra + c), b4 = *reinterpret_cast<const f32x4*>(trb + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float tv = fmaf(a4[e], o[e], b4[e]);
-                    o[e] = TR == 1 ? dip_act_leaky(tv, slope) : dip_act(tv, slope);
-                }
-            }
-            unsigned h[4], m[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b3_split(o[e], h[e], m[e], l[e]);
+            if (TR && valid) o = dip_bf3_transform<TR>(o, tra + c, trb + c, slope);
             unsigned char* base = Abuf + buf * C::A_BYTES + hp * 32 + ((((c4 >> 1) ^ (hp >> 3)) & 1) << 4) + ((c4 & 1) << 3);
-            *reinterpret_cast<u32x2*>(base) = u32x2{(h[0] >> 16) | h[1], (h[2] >> 16) | h[3]};
-            *reinterpret_cast<u32x2*>(base + C::A_PLANE) = u32x2{(m[0] >> 16) | m[1], (m[2] >> 16) | m[3]};
-            *reinterpret_cast<u32x2*>(base + 2 * C::A_PLANE) = u32x2{(l[0] >> 16) | l[1], (l[2] >> 16) | l[3]};
+            b3_split_store<C>(base, o);
         }
     };
     bf16x8 bq[2][NS][3];
@@ -476,17 +441,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_k1_kernel(const DipConvDesc d
     const size_t plane_bytes = (size_t)CoutP * 32;
     typedef bf16x8 (&BSet)[NS][3];
     auto loadB = [&](BSet bs, int ch) {
-        const unsigned char* ub = w3 + (size_t)min(ch, nch - 1) * 3 * plane_bytes;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const unsigned long long b64 = (unsigned long long)(ub + p * plane_bytes);
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)b64);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b64 >> 32));
-            const void* sb = (const void*)(((unsigned long long)hi << 32) | lo);
-#pragma unroll
-            for (int ns = 0; ns < NS; ++ns)
-                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(bs[ns][p]) : "v"(b_voff[ns]), "s"(sb));
-        }
+        b3_load_b(bs, w3 + (size_t)min(ch, nch - 1) * 3 * plane_bytes, plane_bytes, b_voff);
     };
     auto waitA = [&](AReg a) {          // the pixel loads of `a` have landed; the 3 NS weight + 2 pixel loads behind them stay in flight
         asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a[0]), "+v"(a[1]) : "n"(3 * NS + 2));
@@ -509,22 +464,6 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_k1_kernel(const DipConvDesc d
             for (int p = 0; p < 3; ++p) as[ms][p] = *reinterpret_cast<const bf16x8*>(pa + p * C::A_PLANE);
         }
     };
-    auto compute = [&](BSet bs, ASet as) {
-#pragma unroll
-        for (int sm = 4; sm >= 0; --sm) {          // smallest partial products first
-            if ((NT == 6 && sm > 2) || (NT == 8 && sm > 3)) continue;
-#pragma unroll
-            for (int pa = 0; pa < 3; ++pa) {
-                const int pb = sm - pa;
-                if (pb < 0 || pb > 2) continue;
-#pragma unroll
-                for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-                    for (int ns = 0; ns < NS; ++ns)
-                        acc[ms][ns] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as[ms][pa], bs[ns][pb], acc[ms][ns], 0, 0, 0);
-            }
-        }
-    };
 
     // ---- prologue: chunk 0 staged and its fragments read, chunk 1's pixels in flight ----
     loadA(av[0], 0);
@@ -542,7 +481,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf3_k1_kernel(const DipConvDesc d
         loadA(vcur, ch + 2);                       // (chunk ch left this set in unit ch - 1)
         waitA(vnxt);                               // chunk ch + 1, issued a unit ago
         storeA(vnxt, min(ch + 1, nch - 1), nbuf);  // buffer nbuf was last read before the previous barrier
-        compute(bcur, acur);
+        b3_mfma<NT>(acc, bcur, acur);
         __builtin_amdgcn_sched_barrier(0);
         waitB(bnxt);
         __syncthreads();
@@ -609,13 +548,11 @@ __global__ __launch_bounds__(256) void pack_weights_bf3_kernel(const float* __re
             plane = (long long)r.CinP32 * 16;
             o = out + r.dgrad_off + ((long long)(tap * r.nchD + ch) * 3) * plane + (long long)n * 16 + kk;
         }
-        const unsigned uh = __float_as_uint(v) & 0xFFFF0000u;
-        const float r1 = v - __uint_as_float(uh);
-        const unsigned um = __float_as_uint(r1) & 0xFFFF0000u;
-        const float r2 = r1 - __uint_as_float(um);
-        o[0] = (unsigned short)(uh >> 16);
-        o[plane] = (unsigned short)(um >> 16);
-        o[2 * plane] = (unsigned short)(__float_as_uint(r2) >> 16);
+        unsigned h, m, l;
+        dip_bf3_split(v, h, m, l);
+        o[0] = (unsigned short)(h >> 16);
+        o[plane] = (unsigned short)(m >> 16);
+        o[2 * plane] = (unsigned short)(l >> 16);
     }
 }
 
@@ -667,14 +604,10 @@ int bf3_launch_bn(const DipConvDesc& d, int n_base, int ncols, hipStream_t st) {
     return 0;
 }
 
-template <int NT, int TR>
+template <int NT, int TR, int KS>
 int bf3_launch(const DipConvDesc& d, int n_base, int ncols, hipStream_t st) {
-    if (d.ks == 1) {
-        if (dip_cdiv(d.Wout, 16) * dip_cdiv(d.Hout, 8) < 256) return bf3_launch_bn<NT, TR, 64, 1>(d, n_base, ncols, st);
-        return bf3_launch_bn<NT, TR, 128, 1>(d, n_base, ncols, st);
-    }
-    if (dip_cdiv(d.Wout, 16) * dip_cdiv(d.Hout, 8) < 256) return bf3_launch_bn<NT, TR, 64>(d, n_base, ncols, st);
-    return bf3_launch_bn<NT, TR, 128>(d, n_base, ncols, st);
+    return dip_cdiv(d.Wout, 16) * dip_cdiv(d.Hout, 8) < 256 ? bf3_launch_bn<NT, TR, 64, KS>(d, n_base, ncols, st)
+                                                             : bf3_launch_bn<NT, TR, 128, KS>(d, n_base, ncols, st);
 }
 
 }  // namespace
@@ -714,20 +647,10 @@ extern "C" int dip_conv_bf3_cols(const DipConvDesc* dp, int n_base, int ncols, v
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nt = bf3_terms();
     if (nt == 0 || d.wp3 == nullptr) DIP_FAIL("conv_bf3: DIP_CONV_BF3 is off or the descriptor has no split weights (wp3)");
-    const int tr = d.tr.a == nullptr ? 0 : (d.tr.slope > 0.f ? 1 : 2);
-    if (nt == 6) {
-        if (tr == 0) return bf3_launch<6, 0>(d, n_base, ncols, st);
-        if (tr == 1) return bf3_launch<6, 1>(d, n_base, ncols, st);
-        return bf3_launch<6, 2>(d, n_base, ncols, st);
-    }
-    if (nt == 8) {
-        if (tr == 0) return bf3_launch<8, 0>(d, n_base, ncols, st);
-        if (tr == 1) return bf3_launch<8, 1>(d, n_base, ncols, st);
-        return bf3_launch<8, 2>(d, n_base, ncols, st);
-    }
-    if (tr == 0) return bf3_launch<9, 0>(d, n_base, ncols, st);
-    if (tr == 1) return bf3_launch<9, 1>(d, n_base, ncols, st);
-    return bf3_launch<9, 2>(d, n_base, ncols, st);
+    return dip_bf3_dispatch(nt, dip_bf3_tr(d.tr), [&](auto NT, auto TR) {
+        constexpr int T = decltype(NT)::value, R = decltype(TR)::value;
+        return d.ks == 1 ? bf3_launch<T, R, 1>(d, n_base, ncols, st) : bf3_launch<T, R, 3>(d, n_base, ncols, st);
+    });
 }
 
 extern "C" int dip_conv_bf3_terms(void) { return bf3_terms(); }

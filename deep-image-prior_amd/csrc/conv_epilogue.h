@@ -232,3 +232,18 @@ __device__ __forceinline__ void dip_conv_epilogue(const DipConvDesc& d, f32x16 (
         }
     }
 }
+
+// host: the columns of a layer are covered by full 128-wide blocks plus one narrower remainder launch (e.g. the 132-channel
+// data gradient of the decoder convs = 128 + a 32-wide block instead of two 128-wide ones): launch(BN as an integral
+// constant, first column, number of blocks)
+template <class L>
+int dip_launch_col_blocks(int Cout, L&& launch) {
+    const int CoutP = dip_round_up(Cout, 32);
+    const int nfull = CoutP / 128, rem = CoutP - nfull * 128;
+    int rc = 0;
+    if (nfull) rc = launch(std::integral_constant<int, 128>{}, 0, nfull);
+    if (rc || !rem) return rc;
+    if (rem <= 32) return launch(std::integral_constant<int, 32>{}, nfull * 128, 1);
+    if (rem <= 64) return launch(std::integral_constant<int, 64>{}, nfull * 128, 1);
+    return launch(std::integral_constant<int, 128>{}, nfull * 128, 1);
+}

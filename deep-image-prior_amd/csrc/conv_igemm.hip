@@ -27,6 +27,7 @@
 // splitk_finish_kernel sums the slices in a fixed order, adds the bias and emits the statistics.
 #include "dip_common.h"
 #include "conv_epilogue.h"
+#include "lds_dma.h"
 #include "dip_group.h"
 #include <stdlib.h>
 
@@ -63,36 +64,6 @@ struct Cfg {
     static constexpr bool PREFETCH_A = (KS == 1);
 };
 
-__device__ __forceinline__ int map_src(int v, int n_in, int dil, int pad_mode) {
-    const int nv = (n_in - 1) * dil + 1;
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, nv);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), nv - 1);
-    if (v < 0 || v >= nv) return -1;
-    if (dil == 2) {
-        if (v & 1) return -1;
-        v >>= 1;
-    }
-    return v;
-}
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// One LDS-DMA piece: every active lane copies 16 B from its own global address to
-// LDS[m0_base + lane*16].  Issued through inline asm so that hipcc neither counts it nor fences
-// the following ds_reads of the OTHER weight buffer behind it (it cannot prove the two LDS
-// buffers disjoint and would drain vmcnt(0) before every MFMA block); the kernel drains the DMA
-// itself with dma_wait() in front of the barrier that publishes the buffer.  m0 is saved/restored
-// inside the statement (cdna_hip_programming.md section 5.7).
-__device__ __forceinline__ void lds_dma16(const float* gsrc, float* lds_dst_wave_uniform) {
-    const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)lds_dst_wave_uniform);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(base)
-                 : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 template <int KS, int S, int CCH, int BN, bool EXTRA, bool GRP = false>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const DipConvDesc d_, const int ntx, const int ntiles,
                                                             const int CoutP, const int n_base, const int ksplit,
@@ -124,8 +95,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const DipConvDesc d_
     // ---- per-tile source-pixel table (reflection / zero pad / dilation resolved once) ----
     for (int hp = tid; hp < C::NPIX; hp += 256) {
         const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-        const int sr = map_src(ty * C::TH * S + hr - d.off, d.Hin, d.dil, d.pad_mode);
-        const int sc = map_src(tx * C::TW * S + hc - d.off, d.Win, d.dil, d.pad_mode);
+        const int sr = dip_map_src_dil(ty * C::TH * S + hr - d.off, d.Hin, d.dil, d.pad_mode);
+        const int sc = dip_map_src_dil(tx * C::TW * S + hc - d.off, d.Win, d.dil, d.pad_mode);
         srcoff[hp] = (sr < 0 || sc < 0) ? -1 : (sr * d.Win + sc);
     }
     const bool has_tr = d.tr.a != nullptr;
@@ -445,22 +416,16 @@ int launch(const DipConvDesc& d, hipStream_t st, int n_base, int grid_y, int ksp
     return 0;
 }
 
-// N is covered by full 128-wide blocks plus one narrower remainder launch (e.g. the 132-channel
-// data gradient of the decoder convs = 128 + a 32-wide block instead of two 128-wide ones).
+// dip_launch_col_blocks, behind the one-pass N = 160 variant (EXTRA)
 template <int KS, int S, int CCH>
 int launch_bn(const DipConvDesc& d, hipStream_t st, int ksplit, float* ws) {
-    const int CoutP = dip_round_up(d.Cout, 32);
-    const int nfull = CoutP / 128, rem = CoutP - nfull * 128;
-    int rc = 0;
     if constexpr (KS == 3 && S == 1) {
-        if (nfull == 1 && rem == 32 && d.stats == nullptr && (d.Cin % CCH) == 0)
+        if (dip_round_up(d.Cout, 32) == 160 && d.stats == nullptr && (d.Cin % CCH) == 0)
             return launch<KS, S, CCH, 128, true>(d, st, 0, 1, ksplit, ws);      // N = 160 in one pass
     }
-    if (nfull) rc = launch<KS, S, CCH, 128>(d, st, 0, nfull, ksplit, ws);
-    if (rc || !rem) return rc;
-    if (rem <= 32) return launch<KS, S, CCH, 32>(d, st, nfull * 128, 1, ksplit, ws);
-    if (rem <= 64) return launch<KS, S, CCH, 64>(d, st, nfull * 128, 1, ksplit, ws);
-    return launch<KS, S, CCH, 128>(d, st, nfull * 128, 1, ksplit, ws);
+    return dip_launch_col_blocks(d.Cout, [&](auto BN, int n_base, int grid_y) {
+        return launch<KS, S, CCH, decltype(BN)::value>(d, st, n_base, grid_y, ksplit, ws);
+    });
 }
 
 int cch_of(int ks, int stride) {

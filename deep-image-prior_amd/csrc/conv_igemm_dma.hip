@@ -63,26 +63,6 @@ struct DCfg {
     static constexpr int LDS_BYTES = (2 * A_BUF + 2 * B_BUF + NTAB * NPIX + 2 * TRN) * 4;
 };
 
-__device__ __forceinline__ int map_src(int v, int n_in, int dil, int reflect) {
-    const int nv = (n_in - 1) * dil + 1;
-    if (reflect) v = dip_reflect(v, nv);
-    if (v < 0 || v >= nv) return -1;
-    if (dil == 2) {
-        if (v & 1) return -1;
-        v >>= 1;
-    }
-    return v;
-}
-
-#ifdef DIP_CLK_PROFILE
-// debug build only: per-workgroup shader-clock totals of the K-loop segments (wave 0)
-__device__ unsigned long long g_prof[8192 * 16];
-__device__ unsigned g_trace[128 * 8];
-#define PROBE(i) do { } while (0)
-#else
-#define PROBE(i) do { } while (0)
-#endif
-
 // MODE 1 (phase mode, the data gradient of a stride-2 convolution): the descriptor describes the dilated
 // problem (dil == 2, filter d.ks = 2*KS-1, zero padding), the kernel runs it as 4 dense convolutions,
 // one per parity (py, px) of the output pixel: output (2a+py, 2b+px) only sees the filter taps
@@ -106,10 +86,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(const DipConvDes
     constexpr bool PH = (MODE == 1);
     constexpr bool SF = (MODE == 2);
     using C = DCfg<KS, BN, SF ? 4 : 1>;
-#ifdef DIP_CLK_PROFILE
-    const unsigned long long wall0 = wall_clock64(), clk0 = clock64();
-#endif
-    constexpr int KK = KS * KS;
     constexpr int CCH = C::CCH;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                                   // 2 halo buffers
@@ -173,15 +149,15 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(const DipConvDes
             int a0, a1, my, mx;
             sf_dim(ph_ >> 1, a0, a1, my);
             sf_dim(ph_ & 1, a0, a1, mx);
-            const int sr = map_src(2 * (ty * C::TH + hr + my) + (ph_ >> 1), d.Hin, 1, d.pad_mode);
-            const int sc = map_src(2 * (tx * C::TW + hc + mx) + (ph_ & 1), d.Win, 1, d.pad_mode);
+            const int sr = dip_map_src_dil<false>(2 * (ty * C::TH + hr + my) + (ph_ >> 1), d.Hin, 1, d.pad_mode);
+            const int sc = dip_map_src_dil<false>(2 * (tx * C::TW + hc + mx) + (ph_ & 1), d.Win, 1, d.pad_mode);
             srcoff[i] = (sr < 0 || sc < 0) ? -1 : (sr * d.Win + sc);
         }
     } else {
         for (int hp = tid; hp < C::NPIX; hp += 256) {
             const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-            const int sr = map_src(ty * C::TH + hr - offy, d.Hin, PH ? 1 : d.dil, d.pad_mode);
-            const int sc = map_src(tx * C::TW + hc - offx, d.Win, PH ? 1 : d.dil, d.pad_mode);
+            const int sr = dip_map_src_dil<false>(ty * C::TH + hr - offy, d.Hin, PH ? 1 : d.dil, d.pad_mode);
+            const int sc = dip_map_src_dil<false>(tx * C::TW + hc - offx, d.Win, PH ? 1 : d.dil, d.pad_mode);
             srcoff[hp] = (sr < 0 || sc < 0) ? -1 : (sr * d.Win + sc);
         }
     }
@@ -405,10 +381,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(const DipConvDes
 #pragma unroll
     for (int i = 0; i < C::A_SLOTS; ++i) nA += (wave * 64 + i * 256 < C::NPIX * 8) ? 1 : 0;
     int a_state = 0;                       // next halo: 0 none/ready, 1 in flight, 2 landed but not fixed up yet
-#ifdef DIP_CLK_PROFILE
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long tstart = clock64();
-#endif
 
     // One K step of 8 channels: the fragments of both operands (lane = 4 consecutive channels of its
     // pixel / column -> 4 MFMAs per ds_read_b128 pair).
@@ -621,10 +593,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(const DipConvDes
             have_f0 = false;
         }
     }
-#ifdef DIP_CLK_PROFILE
-    const unsigned long long clk_kend = clock64();
-    prof[7] = clk_kend - tstart;
-#endif
 
     // ---- epilogue (conv_epilogue.h) ----
     if (ksplit > 1) {
@@ -659,19 +627,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(const DipConvDes
         epi.full = (epi.rows_left >= C::TH) && (epi.cols_left >= C::TW);
     }
     dip_conv_epilogue<C, BN>(d, acc, epi, n0, wn, wm, l31, half, tid, tile, CoutP, smem);
-#ifdef DIP_CLK_PROFILE
-    __syncthreads();
-    if (tid == 0 && blockIdx.x < 8192) {
-        unsigned long long* o = g_prof + (size_t)blockIdx.x * 16;
-        for (int i = 0; i < 8; ++i) o[i] = prof[i];
-        o[8] = wall0;
-        o[9] = wall_clock64();
-        o[10] = __builtin_amdgcn_s_getreg(63492);      // HW_ID
-        o[11] = __builtin_amdgcn_s_getreg(63508);      // XCC_ID
-        o[12] = tstart - clk0;                          // prologue cycles
-        o[13] = clock64() - clk_kend;                   // epilogue cycles
-    }
-#endif
 }
 
 template <int KS, int BN, bool TR, int MODE = 0>
@@ -703,14 +658,9 @@ int launch(const DipConvDesc& d, hipStream_t st, int n_base, int grid_y, int ksp
 
 template <int KS, int MODE = 0>
 int launch_bn(const DipConvDesc& d, hipStream_t st, int ksplit, float* ws) {
-    const int CoutP = dip_round_up(d.Cout, 32);
-    const int nfull = CoutP / 128, rem = CoutP - nfull * 128;
-    int rc = 0;
-    if (nfull) rc = launch<KS, 128, MODE>(d, st, 0, nfull, ksplit, ws);
-    if (rc || !rem) return rc;
-    if (rem <= 32) return launch<KS, 32, MODE>(d, st, nfull * 128, 1, ksplit, ws);
-    if (rem <= 64) return launch<KS, 64, MODE>(d, st, nfull * 128, 1, ksplit, ws);
-    return launch<KS, 128, MODE>(d, st, nfull * 128, 1, ksplit, ws);
+    return dip_launch_col_blocks(d.Cout, [&](auto BN, int n_base, int grid_y) {
+        return launch<KS, decltype(BN)::value, MODE>(d, st, n_base, grid_y, ksplit, ws);
+    });
 }
 
 }  // namespace
@@ -733,15 +683,6 @@ extern "C" int dip_conv_dma_eligible(const DipConvDesc* dp) {
     if (has_tr && d.ks == 1 && (d.off != 0 || d.dil != 1)) return 0;
     return 1;
 }
-
-#ifdef DIP_CLK_PROFILE
-extern "C" int dip_debug_trace_read(void* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_trace), sizeof(unsigned) * 128 * 8);
-}
-extern "C" int dip_debug_prof_read(void* dst, int nwg) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_prof), (size_t)nwg * 16 * sizeof(unsigned long long));
-}
-#endif
 
 // one 128-column block starting at column n_base (3x3 only): the 132-column data gradients run as
 // conv_thin4 (columns 0..3) + this (columns 4..131)

@@ -82,6 +82,32 @@ __device__ __forceinline__ int dip_reflect(int v, int n) {
     if (v >= n) v = 2 * (n - 1) - v;
     return v;
 }
+// Source index of position v of the padded (and, dil == 2, zero-interleaved: the data gradient of a stride-2 convolution)
+// input of n_in samples: the padding rule folds v into the valid range; -1 = reads a zero.  REPLICATE = false is the form of
+// a kernel that replication padding is never sent to (conv_igemm_dma.hip: dip_conv_dma_eligible): one compare less, every
+// pad_mode other than DIP_PAD_ZERO is taken as reflection.
+template <bool REPLICATE = true>
+__device__ __forceinline__ int dip_map_src_dil(int v, int n_in, int dil, int pad_mode) {
+    const int nv = (n_in - 1) * dil + 1;
+    if constexpr (REPLICATE) {
+        if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, nv);
+        else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), nv - 1);
+    } else {
+        if (pad_mode != DIP_PAD_ZERO) v = dip_reflect(v, nv);
+    }
+    if (v < 0 || v >= nv) return -1;
+    if (dil == 2) {
+        if (v & 1) return -1;
+        v >>= 1;
+    }
+    return v;
+}
+// the undilated form
+__device__ __forceinline__ int dip_map_src(int v, int n_in, int pad_mode) {
+    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
+    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
+    return (v < 0 || v >= n_in) ? -1 : v;
+}
 
 // Chan et al. pairwise combination of (count, mean, M2)
 __device__ __forceinline__ void dip_chan(float& na, float& ma, float& Ma, float nb, float mb, float Mb) {

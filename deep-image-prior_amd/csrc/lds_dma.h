@@ -4,6 +4,12 @@
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
+// One LDS-DMA piece: every active lane copies 16 B from its own global address to
+// LDS[m0_base + lane*16].  Issued through inline asm so that hipcc neither counts it nor fences
+// the following ds_reads of the OTHER weight buffer behind it (it cannot prove the two LDS
+// buffers disjoint and would drain vmcnt(0) before every MFMA block); the kernel drains the DMA
+// itself with dma_wait() in front of the barrier that publishes the buffer.  m0 is saved/restored
+// inside the statement (cdna_hip_programming.md section 5.7).
 __device__ __forceinline__ void lds_dma16(const float* gsrc, float* lds_dst_wave_uniform) {
     const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptr_t)lds_dst_wave_uniform);
     unsigned keep;

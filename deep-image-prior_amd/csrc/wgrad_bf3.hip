@@ -26,12 +26,10 @@
 // (dip_conv_wgrad_tail): 2 MFMAs per K step instead of 9 with 28 of 32 rows idle.
 #include "dip_common.h"
 #include "dip_group.h"
+#include "bf3.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef DIP_W3_PROFILE
 // per-wave cycle sums of the ping-pong kernel's phases (s_memtime ticks = shader cycles): [workgroup][wave][8]
@@ -61,21 +59,17 @@ struct W3Cfg {
     static constexpr int LDS_BYTES = 3 * U_PLANE + 3 * D_PLANE + 2 * 512 * 4;      // + the transform tables
 };
 
-__device__ __forceinline__ int w3_map_src(int v, int n_in, int pad_mode) {
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
-    return (v < 0 || v >= n_in) ? -1 : v;
+// staging: the split halves of two horizontally adjacent pixels x 4 channels -> the pixel pair packed into one dword per
+// (channel, plane): the operands are TRANSPOSED in LDS, [plane][channel][pixel] with these pitches in bytes
+__device__ __forceinline__ void w3_store_planes(unsigned char* base, const unsigned (&h)[2][4], const unsigned (&m)[2][4], const unsigned (&l)[2][4],
+                                                int ch_pitch, int plane_pitch) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        *reinterpret_cast<unsigned*>(base + e * ch_pitch) = dip_bf3_pack2(h[0][e], h[1][e]);
+        *reinterpret_cast<unsigned*>(base + e * ch_pitch + plane_pitch) = dip_bf3_pack2(m[0][e], m[1][e]);
+        *reinterpret_cast<unsigned*>(base + e * ch_pitch + 2 * plane_pitch) = dip_bf3_pack2(l[0][e], l[1][e]);
+    }
 }
-
-// a == h + m + l exactly (three bf16 numbers, by truncation); returned in the HIGH halves
-__device__ __forceinline__ void w3_split(float a, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned uh = __float_as_uint(a) & 0xFFFF0000u;
-    const float r1 = a - __uint_as_float(uh);
-    const unsigned um = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(um);
-    h = uh; m = um; l = __float_as_uint(r2) & 0xFFFF0000u;
-}
-
 // The three horizontal taps of one (tile row, tap row) out of the 16-byte-aligned windows w0 (8 pixels) + w1 (2 more) of a halo
 // row, all partial products, smallest first, the three taps' accumulators taking turns MFMA by MFMA.  Per accumulator the
 // order of the products is that of the 4-wave form, so the result is bit-identical.  (The rotation was written on the
@@ -93,22 +87,16 @@ __device__ __forceinline__ void w3_taps_of_row(const u32x4 (&w0)[3], const unsig
                                                      __builtin_amdgcn_alignbyte(w0[p][3], w0[p][2], 2), __builtin_amdgcn_alignbyte(w1[p], w0[p][3], 2)});
         a[2][p] = __builtin_bit_cast(bf16x8, u32x4{w0[p][1], w0[p][2], w0[p][3], w1[p]});
     }
-#pragma unroll
-    for (int sm = 4; sm >= 0; --sm) {               // smallest partial products first
-        if ((NT == 6 && sm > 2) || (NT == 8 && sm > 3)) continue;
-#pragma unroll
-        for (int pa = 0; pa < 3; ++pa) {
-            const int pb = sm - pa;
-            if (pb < 0 || pb > 2) continue;
-            // (sched_barrier 0x7F6: everything but MFMAs may cross, so the MFMAs stay in this order)
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][pa], b[pb], acc0, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0x7F6);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][pa], b[pb], acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0x7F6);
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][pa], b[pb], acc2, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0x7F6);
-        }
-    }
+    dip_bf3_products<NT>([&](auto PA, auto PB) {
+        constexpr int pa = decltype(PA)::value, pb = decltype(PB)::value;
+        // (sched_barrier 0x7F6: everything but MFMAs may cross, so the MFMAs stay in this order)
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][pa], b[pb], acc0, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0x7F6);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][pa], b[pb], acc1, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0x7F6);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][pa], b[pb], acc2, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0x7F6);
+    });
 }
 
 template <int NT, int TR>
@@ -159,11 +147,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf3_v1_kernel(const DipWgradDesc
             const int s = tid + i * 256;
             const int cg = s / 36, rem = s - cg * 36, hr = rem / 9, pp = rem - hr * 9;
             const int c = c0 + cg * 4;
-            const int sr = w3_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
+            const int sr = dip_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
             const bool okc = s < C::U_PAIRS && c < d.Cin && sr >= 0;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const int sc = w3_map_src(tx * C::TW + 2 * pp + q - d.off, d.Win, d.pad_mode);
+                const int sc = dip_map_src(tx * C::TW + 2 * pp + q - d.off, d.Win, d.pad_mode);
                 const bool ok = okc && sc >= 0;
                 // unconditional load from a clamped address; commit() zeroes what is padding (same predicate)
                 ur[i][q] = *reinterpret_cast<const f32x4*>(d.x + ((size_t)(ok ? sr : 0) * d.Win + (ok ? sc : 0)) * d.Cx + (ok ? c : 0));
@@ -191,14 +179,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf3_v1_kernel(const DipWgradDesc
             if (s < C::U_PAIRS) {
                 const int cg = s / 36, rem = s - cg * 36, hr = rem / 9, pp = rem - hr * 9;
                 const int c = c0 + cg * 4;
-                const int sr = w3_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
+                const int sr = dip_map_src(ty * C::TH + hr - d.off, d.Hin, d.pad_mode);
                 unsigned h[2][4], m[2][4], l[2][4];
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const int sc = w3_map_src(tx * C::TW + 2 * pp + q - d.off, d.Win, d.pad_mode);
+                    const int sc = dip_map_src(tx * C::TW + 2 * pp + q - d.off, d.Win, d.pad_mode);
                     const bool ok = c < d.Cin && sr >= 0 && sc >= 0;
                     f32x4 v = ur[i][q];
-                    if (TR) {
+                    if (TR) {       // (dip_bf3_transform, spelled out: through the helper hipcc schedules this kernel's TR == 2 form differently)
                         const f32x4 a4 = *reinterpret_cast<const f32x4*>(tra + cg * 4), b4 = *reinterpret_cast<const f32x4*>(trb + cg * 4);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -207,15 +195,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf3_v1_kernel(const DipWgradDesc
                         }
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) w3_split(ok ? v[e] : 0.f, h[q][e], m[q][e], l[q][e]);
+                    for (int e = 0; e < 4; ++e) dip_bf3_split(ok ? v[e] : 0.f, h[q][e], m[q][e], l[q][e]);
                 }
-                unsigned char* base = Us + (cg * 4) * C::U_CH + hr * C::U_ROW + pp * 4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH) = (h[0][e] >> 16) | h[1][e];
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH + C::U_PLANE) = (m[0][e] >> 16) | m[1][e];
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH + 2 * C::U_PLANE) = (l[0][e] >> 16) | l[1][e];
-                }
+                w3_store_planes(Us + (cg * 4) * C::U_CH + hr * C::U_ROW + pp * 4, h, m, l, C::U_CH, C::U_PLANE);
             }
         }
 #pragma unroll
@@ -233,16 +215,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf3_v1_kernel(const DipWgradDesc
                 for (int e = 0; e < 4; ++e) {
                     const float v = ok ? dr[i][q][e] : 0.f;
                     bs[i][e] += v;
-                    w3_split(v, h[q][e], m[q][e], l[q][e]);
+                    dip_bf3_split(v, h[q][e], m[q][e], l[q][e]);
                 }
             }
-            unsigned char* base = Ds + (cg * 4) * C::D_CH + r * C::D_ROW + pp * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH) = (h[0][e] >> 16) | h[1][e];
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH + C::D_PLANE) = (m[0][e] >> 16) | m[1][e];
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH + 2 * C::D_PLANE) = (l[0][e] >> 16) | l[1][e];
-            }
+            w3_store_planes(Ds + (cg * 4) * C::D_CH + r * C::D_ROW + pp * 4, h, m, l, C::D_CH, C::D_PLANE);
         }
     };
 
@@ -286,16 +262,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf3_v1_kernel(const DipWgradDesc
                             a[p] = __builtin_bit_cast(bf16x8, v);
                         }
                         const int t = ky * 3 + kx;
-#pragma unroll
-                        for (int sm = 4; sm >= 0; --sm) {               // smallest partial products first
-                            if ((NT == 6 && sm > 2) || (NT == 8 && sm > 3)) continue;
-#pragma unroll
-                            for (int pa = 0; pa < 3; ++pa) {
-                                const int pb = sm - pa;
-                                if (pb < 0 || pb > 2) continue;
-                                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pa], b[pb], acc[t], 0, 0, 0);
-                            }
-                        }
+                        dip_bf3_products<NT>([&](auto PA, auto PB) {
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[decltype(PA)::value], b[decltype(PB)::value], acc[t], 0, 0, 0);
+                        });
                     }
                     // one halo row at a time: hoisting the windows of later rows above these MFMAs spills the accumulators
                     __builtin_amdgcn_sched_barrier(0);
@@ -338,12 +307,9 @@ int w3_launch_v1(const DipWgradDesc& d, hipStream_t st) {
     using C = W3Cfg;
     auto kern = wgrad_bf3_v1_kernel<NT, TR>;
     static bool attr_set[16] = {};
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
+    if (dip_once_per_device(attr_set)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { dip_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set[dev] = true;
     }
     const int ntx = dip_cdiv(d.Wout, C::TW), nty = dip_cdiv(d.Hout, C::TH);
     const int CinP = dip_round_up(d.Cin, 32), CoutP = dip_round_up(d.Cout, 32);
@@ -464,11 +430,11 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const DipWgradDesc d, co
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int sr = w3_map_src(ty * C::TH + u_hr[i] - d.off, d.Hin, d.pad_mode);
+                const int sr = dip_map_src(ty * C::TH + u_hr[i] - d.off, d.Hin, d.pad_mode);
                 const bool okc = u_valid[i] && sr >= 0;
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const int sc = w3_map_src(tx * C::TW + 2 * u_pp[i] + q - d.off, d.Win, d.pad_mode);
+                    const int sc = dip_map_src(tx * C::TW + 2 * u_pp[i] + q - d.off, d.Win, d.pad_mode);
                     const bool ok = okc && sc >= 0;
                     // unconditional load from a clamped address; commit() zeroes what is padding (same predicate)
                     pu[i][q] = d.x + ((size_t)(ok ? sr : 0) * d.Win + (ok ? sc : 0)) * d.Cx + (ok ? u_c : 0);
@@ -500,10 +466,10 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const DipWgradDesc d, co
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int sr = w3_map_src(ty * C::TH + u_hr[i] - d.off, d.Hin, d.pad_mode);
+                const int sr = dip_map_src(ty * C::TH + u_hr[i] - d.off, d.Hin, d.pad_mode);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    const int sc = w3_map_src(tx * C::TW + 2 * u_pp[i] + q - d.off, d.Win, d.pad_mode);
+                    const int sc = dip_map_src(tx * C::TW + 2 * u_pp[i] + q - d.off, d.Win, d.pad_mode);
                     oku[i][q] = u_valid[i] && sr >= 0 && sc >= 0;
                 }
             }
@@ -518,25 +484,11 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const DipWgradDesc d, co
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     f32x4 v = ur[i][q];
-                    if (TR) {
-                        const f32x4 a4 = *reinterpret_cast<const f32x4*>(tra + grp * 32 + (tg & 7) * 4);
-                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(trb + grp * 32 + (tg & 7) * 4);
+                    v = dip_bf3_transform<TR>(v, tra + grp * 32 + (tg & 7) * 4, trb + grp * 32 + (tg & 7) * 4, slope);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float tv = fmaf(a4[e], v[e], b4[e]);
-                            v[e] = TR == 1 ? dip_act_leaky(tv, slope) : dip_act(tv, slope);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w3_split(oku[i][q] ? v[e] : 0.f, h[q][e], m[q][e], l[q][e]);
+                    for (int e = 0; e < 4; ++e) dip_bf3_split(oku[i][q] ? v[e] : 0.f, h[q][e], m[q][e], l[q][e]);
                 }
-                unsigned char* base = Bs + u_lds[i];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH) = (h[0][e] >> 16) | h[1][e];
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH + U_PLANE2) = (m[0][e] >> 16) | m[1][e];
-                    *reinterpret_cast<unsigned*>(base + e * C::U_CH + 2 * U_PLANE2) = (l[0][e] >> 16) | l[1][e];
-                }
+                w3_store_planes(Bs + u_lds[i], h, m, l, C::U_CH, U_PLANE2);
             }
         }
         {
@@ -547,16 +499,10 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const DipWgradDesc d, co
                 for (int e = 0; e < 4; ++e) {
                     const float v = okd[q] ? dr[q][e] : 0.f;
                     bs[e] += v;
-                    w3_split(v, h[q][e], m[q][e], l[q][e]);
+                    dip_bf3_split(v, h[q][e], m[q][e], l[q][e]);
                 }
             }
-            unsigned char* base = Bs + d_lds;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH) = (h[0][e] >> 16) | h[1][e];
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH + C::D_PLANE) = (m[0][e] >> 16) | m[1][e];
-                *reinterpret_cast<unsigned*>(base + e * C::D_CH + 2 * C::D_PLANE) = (l[0][e] >> 16) | l[1][e];
-            }
+            w3_store_planes(Bs + d_lds, h, m, l, C::D_CH, C::D_PLANE);
         }
     };
 
@@ -695,12 +641,9 @@ int w3_launch(const DipWgradDesc& d, hipStream_t st) {
     constexpr int LDS2 = 2 * (3 * 64 * C::U_CH + 3 * C::D_PLANE) + 2 * 64 * 4;
     auto kern = wgrad_bf3_kernel<NT, TR>;
     static bool attr_set[16] = {};
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
+    if (dip_once_per_device(attr_set)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { dip_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set[dev] = true;
     }
     const int ntx = dip_cdiv(d.Wout, C::TW), nty = dip_cdiv(d.Hout, C::TH);
     const int CinP = dip_round_up(d.Cin, 32), CoutP = dip_round_up(d.Cout, 32);
@@ -745,20 +688,14 @@ extern "C" int dip_wgrad_bf3(const DipWgradDesc* dp, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nt = dip_conv_bf3_terms();
     if (nt == 0) DIP_FAIL("wgrad_bf3: the bf16-pipe arithmetic is switched off (DIP_CONV_BF3=0)");
-    const int tr = d.tr.a == nullptr ? 0 : (d.tr.slope > 0.f ? 1 : 2);
-    int rc;
     // DIP_WGRAD_BF3_V1=1: the round-4 form of the kernel (4 waves, two workgroups per CU, one accumulator at a time) for every
     // layer: the REFERENCE of the bit-identity test (tests/test_bf3_gpu.py) and of A/B runs.  =2: only below 2048 tiles.
     static const int v1_mode = [] { const char* e = getenv("DIP_WGRAD_BF3_V1"); return e ? atoi(e) : 0; }();
     const bool v1 = v1_mode == 1 || (v1_mode == 2 && dip_cdiv(d.Wout, 16) * dip_cdiv(d.Hout, 2) < 2048);
-    if (v1) {
-        if (nt == 6) rc = tr == 0 ? w3_launch_v1<6, 0>(d, st) : (tr == 1 ? w3_launch_v1<6, 1>(d, st) : w3_launch_v1<6, 2>(d, st));
-        else if (nt == 8) rc = tr == 0 ? w3_launch_v1<8, 0>(d, st) : (tr == 1 ? w3_launch_v1<8, 1>(d, st) : w3_launch_v1<8, 2>(d, st));
-        else rc = tr == 0 ? w3_launch_v1<9, 0>(d, st) : (tr == 1 ? w3_launch_v1<9, 1>(d, st) : w3_launch_v1<9, 2>(d, st));
-    } else
-    if (nt == 6) rc = tr == 0 ? w3_launch<6, 0>(d, st) : (tr == 1 ? w3_launch<6, 1>(d, st) : w3_launch<6, 2>(d, st));
-    else if (nt == 8) rc = tr == 0 ? w3_launch<8, 0>(d, st) : (tr == 1 ? w3_launch<8, 1>(d, st) : w3_launch<8, 2>(d, st));
-    else rc = tr == 0 ? w3_launch<9, 0>(d, st) : (tr == 1 ? w3_launch<9, 1>(d, st) : w3_launch<9, 2>(d, st));
+    const int rc = dip_bf3_dispatch(nt, dip_bf3_tr(d.tr), [&](auto NT, auto TR) {
+        constexpr int T = decltype(NT)::value, R = decltype(TR)::value;
+        return v1 ? w3_launch_v1<T, R>(d, st) : w3_launch<T, R>(d, st);
+    });
     if (rc) return rc;
     // the <= 4-channel tail of a 132-channel layer: the fp32 kernel's (tap, channel)-packed phase 2 on its own
     if ((d.Cin & 31) >= 1 && (d.Cin & 31) <= 4 && d.Cin > 32) return dip_conv_wgrad_tail(dp, stream);

@@ -273,3 +273,70 @@ def test_wgrad_bf3_pingpong_is_bit_identical_to_the_round4_kernel(dev, tmp_path)
         a, b = out["new"][k], out["v1"][k]
         assert np.isfinite(a).all(), k
         assert np.array_equal(a, b), (k, float(np.abs(a.astype(np.float64) - b).max()))
+
+
+# kernel form -> (Cin, Cout, H, W): the smallest layer each form takes
+TR2_FORMS = {
+    "fwd_n64": (20, 128, 64, 192),        # 96 tiles, the eligibility floor: 64-column form; 16 + 4 channels: the packed 4-channel tail
+    "fwd_n128": (16, 128, 128, 256),      # 256 tiles, the switch to the 128-column form
+    "wgrad": (32, 128, 64, 256),          # 512 tiles of 2 x 16, Cin >= 32, Cout >= 97: the floor of wgrad_bf3
+}
+_tr2_refs = {}
+
+
+def _tr2_ref(form, code):
+    """Inputs and the fp64 reference of one (form, activation code), computed once and shared by the `terms` cases."""
+    if (form, code) not in _tr2_refs:
+        Cin, Cout, Hh, Ww = TR2_FORMS[form]
+        x, w, b, a, bb = _mk((Cin, Cout, 3, 1, REFLECT, Hh, Ww, True), 3)
+        if form == "wgrad":
+            ww = w.double().requires_grad_(True)
+            y = _ref_conv(_apply_tr(x, a, bb, code, torch.float64), ww, b, 1, REFLECT, torch.float64)
+            dy = torch.randn(y.shape, generator=torch.Generator().manual_seed(9))
+            (y * dy.double()).sum().backward()
+            ref = ww.grad
+        else:
+            dy = None
+            ref = _ref_conv(_apply_tr(x, a, bb, code, torch.float64), w, b, 1, REFLECT, torch.float64)
+        _tr2_refs[form, code] = (x, w, b, a, bb, dy, ref)
+    return _tr2_refs[form, code]
+
+
+@pytest.mark.parametrize("terms", [9, 8])
+@pytest.mark.parametrize("code", [-1.0, -2.0], ids=["swish", "elu"])
+@pytest.mark.parametrize("form", list(TR2_FORMS))
+def test_bf3_kernels_with_swish_and_elu_transform(dev, form, code, terms):
+    """The TR == 2 instantiations (producer activation Swish / ELU: DipTransform.slope = -1 / -2) of conv_bf3_kernel in both
+    column forms and of wgrad_bf3_kernel, which every case above (slope 0.2: TR == 1) leaves out.  Criterion of those cases:
+    the error against fp64 is at most 1.5 x the error of the fp32-MFMA kernels (dip_conv_bf3_set_terms(0)) on the same inputs."""
+    import ctypes as C
+    Cin, Cout, Hh, Ww = TR2_FORMS[form]
+    x, w, b, a, bb, dy, ref64 = _tr2_ref(form, code)
+    tr = (a.to(dev), bb.to(dev), code)
+    lib = N.lib()
+    if form == "wgrad":
+        N.check(lib.dip_conv_bf3_set_terms(terms))
+        try:
+            n, g, cb = N.wgrad_plan2(Hh, Ww, Cin, Cout, 3, 1)
+            d = N.DipWgradDesc(None, Hh, Ww, N.round_up(Cin, 4), Cin, N.DipTransform(None, None, 1.0), None, Hh, Ww, N.round_up(Cout, 4),
+                               Cout, 3, 1, REFLECT, 1, None, None, n, g, cb)
+            assert lib.dip_wgrad_bf3_eligible(C.byref(d)) == 1, "descriptor not taken by the bf16-pipe weight gradient"
+            got, _ = H.conv_wgrad(x.to(dev), dy.to(dev), 3, 1, REFLECT, tr, nsplit="plan")
+            lib.dip_conv_bf3_set_terms(0)
+            got32, _ = H.conv_wgrad(x.to(dev), dy.to(dev), 3, 1, REFLECT, tr, nsplit="plan")       # the fp32-MFMA kernel
+        finally:
+            lib.dip_conv_bf3_set_terms(-1)
+    else:
+        ntiles = lib.dip_conv_ntiles(Hh, Ww)
+        assert (96 <= ntiles < 256) if form == "fwd_n64" else ntiles >= 256
+        got, _ = H.conv_bf3(x.to(dev), w.to(dev), b.to(dev), REFLECT, tr, terms=terms)       # (asserts that the bf16-pipe kernel takes it)
+        N.check(lib.dip_conv_bf3_set_terms(0))
+        try:
+            got32 = H.conv_fwd(x.to(dev), w.to(dev), b.to(dev), 1, REFLECT, tr)               # the fp32-MFMA kernel, same inputs
+        finally:
+            lib.dip_conv_bf3_set_terms(-1)
+    assert torch.isfinite(got).all()
+    e3 = (got.cpu().double() - ref64).pow(2).sum().sqrt().item()
+    e32 = (got32.cpu().double() - ref64).pow(2).sum().sqrt().item()
+    print(f"{form} code {code} terms {terms}: bf16-pipe error {e3:.3e}, fp32-MFMA error {e32:.3e}, |ref| {ref64.pow(2).sum().sqrt().item():.3e}")
+    assert e3 <= 1.5 * e32, f"bf16-pipe error {e3:.3e} vs fp32-MFMA error {e32:.3e}"

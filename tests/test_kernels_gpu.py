@@ -99,7 +99,12 @@ def _apply_tr(x, a, b, slope, dtype):
     if a is None:
         return x.to(dtype)
     t = x.to(dtype) * a.to(dtype).view(1, -1, 1, 1) + b.to(dtype).view(1, -1, 1, 1)
-    return torch.maximum(t, slope * t)
+    if slope >= 0:
+        return torch.maximum(t, slope * t)
+    # the activation codes of DipTransform.slope (include/dip_hip.h): -1 Swish, -2 ELU(alpha = 1), -3 ReLU
+    acts = {-1.0: lambda: t * torch.sigmoid(t), -2.0: lambda: F.elu(t), -3.0: lambda: torch.relu(t)}
+    assert float(slope) in acts, f"unknown activation code {slope}"
+    return acts[float(slope)]()
 
 
 @pytest.mark.parametrize("split", [False, True], ids=["onepass", "splitk"])
