@@ -351,3 +351,120 @@ def conv_bf3(x, w, bias, pad_mode, tr=(None, None, 1.0), terms=9, dgrad_of=None)
         return gx
     finally:
         lib.dip_conv_bf3_set_terms(-1)
+
+
+# ----------------------------------------------------------------------------- closure-side kernels
+SENTINEL = -777.0          # value of the few extra trailing elements every output buffer below carries
+_TAIL = 8
+
+
+def guarded(n, dev):
+    """NaN-filled float buffer of n elements followed by _TAIL sentinel elements (see tail_untouched)."""
+    t = torch.full((n + _TAIL,), float("nan"), dtype=torch.float32, device=dev)
+    t[n:] = SENTINEL
+    return t
+
+
+def tail_untouched(t):
+    return bool(torch.all(t[-_TAIL:] == SENTINEL))
+
+
+def loss_head_desc(u, w, bias, target, mask, sigmoid, tr, Cu=None):
+    """DipLossHeadDesc of the fused loss head over u [1,Cin,Hh,Ww] (input of the 1x1 output conv, stored NHWC with channel
+    stride Cu: channels Cin..round_up(Cin, 4) zero, anything beyond NaN), w [Cout,Cin], bias [Cout] | None, target
+    [Cout,HW], mask [1 | Cout, HW] | None, tr = (a, b, slope).  Returns (desc, buffers); buffers keeps out / partials /
+    loss (each NaN-filled with a sentinel tail) and everything the descriptor points at alive."""
+    lib = N.lib()
+    dev = u.device
+    _, Cin, Hh, Ww = u.shape
+    HW = Hh * Ww
+    Cout = w.shape[0]
+    C4 = round_up(Cin, 4)
+    Cu = Cu or C4
+    ub = to_nhwc(u, Cu)
+    if Cu > C4:
+        ub[:, :, C4:] = float("nan")
+    trd, keep = transform(*tr)
+    wd = w.contiguous().float()
+    bd = bias.contiguous().float() if bias is not None else None
+    td = target.contiguous().float()
+    md = mask.contiguous().float() if mask is not None else None
+    nblk = lib.dip_loss_head_nblk(HW, Cin)
+    b = dict(u=ub, tr=keep, w=wd, bias=bd, target=td, mask=md, out=guarded(Cout * HW, dev), partials=guarded(nblk, dev),
+             loss=guarded(1, dev), Cout=Cout, HW=HW)
+    d = N.DipLossHeadDesc(ub.data_ptr(), Cu, Cin, trd, wd.data_ptr(), bd.data_ptr() if bd is not None else None, Cout, HW,
+                          1 if sigmoid else 0, td.data_ptr(), md.data_ptr() if md is not None else None,
+                          md.shape[0] if md is not None else 0, b["out"].data_ptr(), b["partials"].data_ptr(), nblk,
+                          b["loss"].data_ptr())
+    return d, b
+
+
+def loss_head(u, w, bias, target, mask, sigmoid, tr, Cu=None, gscale=None):
+    """dip_loss_head_fwd + dip_loss_head_bwd through the descriptor (see loss_head_desc); gscale: None (NULL) or a float
+    (a device scalar).  Returns (loss [], out [Cout,HW], dy [HW, round_up(Cout, 4)]), all on the device."""
+    lib = N.lib()
+    dev = u.device
+    d, b = loss_head_desc(u, w, bias, target, mask, sigmoid, tr, Cu)
+    Cout, HW = b["Cout"], b["HW"]
+    Cy = round_up(Cout, 4)
+    dy = guarded(HW * Cy, dev)
+    gs = torch.full((1,), float(gscale), dtype=torch.float32, device=dev) if gscale is not None else None
+    N.check(lib.dip_loss_head_fwd(C.byref(d), stream(dev)), "loss_head_fwd")
+    N.check(lib.dip_loss_head_bwd(C.byref(d), gs.data_ptr() if gs is not None else None, dy.data_ptr(), Cy, stream(dev)),
+            "loss_head_bwd")
+    torch.cuda.synchronize()
+    for name in ("out", "partials", "loss"):
+        assert tail_untouched(b[name]), f"loss_head: wrote past the end of {name}"
+    assert tail_untouched(dy), "loss_head_bwd: wrote past the end of dy"
+    return b["loss"][0].clone(), b["out"][:Cout * HW].view(Cout, HW).clone(), dy[:HW * Cy].view(HW, Cy).clone()
+
+
+def pool2(x, mode, want_stats):
+    """dip_{avg,max}pool2_fwd on x [1,C,H,W] -> y [1,C,H//2,W//2]; want_stats: also the (mean, rstd) rows [2,C] that
+    dip_bn_finalize makes of the launch's {count, mean, M2} partials (None otherwise)."""
+    lib = N.lib()
+    dev = x.device
+    _, Cc, Hh, Ww = x.shape
+    Hl, Wl = Hh // 2, Ww // 2
+    Cs = round_up(Cc, 4)
+    xb = to_nhwc(x)
+    y = guarded(Hl * Wl * Cs, dev)
+    nblk = lib.dip_upcat_nblk(Hl, Wl, Cc)
+    stats = guarded(nblk * 3 * Cs, dev) if want_stats else None
+    fwd = {"avg": lib.dip_avgpool2_fwd, "max": lib.dip_maxpool2_fwd}[mode]
+    N.check(fwd(xb.data_ptr(), Hh, Ww, Cs, Cc, y.data_ptr(), Cs, stats.data_ptr() if want_stats else None, nblk,
+                stream(dev)), mode + "pool2_fwd")
+    mr = None
+    if want_stats:
+        state = guarded(4 * Cs, dev)
+        gam, bet = torch.ones(Cc, device=dev), torch.zeros(Cc, device=dev)
+        N.check(lib.dip_bn_finalize(stats.data_ptr(), nblk, Cs, Cc, gam.data_ptr(), bet.data_ptr(), 1e-5, 0.1,
+                                    state.data_ptr(), Cs, None, None, stream(dev)), "bn_finalize")
+        torch.cuda.synchronize()
+        assert tail_untouched(stats) and tail_untouched(state), "pool2_fwd: wrote past the end of the statistics"
+        mr = state[:4 * Cs].view(4, Cs)[:2, :Cc].clone()
+    torch.cuda.synchronize()
+    assert tail_untouched(y), "pool2_fwd: wrote past the end of y"
+    yv = y[:Hl * Wl * Cs]
+    assert torch.all(yv.view(Hl, Wl, Cs)[:, :, Cc:] == 0), "pad channels must be written as zeros"
+    return from_nhwc(yv, Cc, Hl, Wl), mr
+
+
+def pool2_bwd(dy, x, mode):
+    """dip_{avg,max}pool2_bwd: dy [1,C,H//2,W//2], x [1,C,H,W] (the pooled layer's input) -> dx [1,C,H,W]."""
+    lib = N.lib()
+    dev = x.device
+    _, Cc, Hh, Ww = x.shape
+    Cs = round_up(Cc, 4)
+    gb, xb = to_nhwc(dy), to_nhwc(x)
+    dx = guarded(Hh * Ww * Cs, dev)
+    if mode == "max":
+        N.check(lib.dip_maxpool2_bwd(gb.data_ptr(), xb.data_ptr(), Hh, Ww, Cs, Cs, Cc, dx.data_ptr(), Cs, stream(dev)),
+                "maxpool2_bwd")
+    else:
+        N.check(lib.dip_avgpool2_bwd(gb.data_ptr(), Hh, Ww, Cs, Cc, dx.data_ptr(), Cs, stream(dev)), "avgpool2_bwd")
+    torch.cuda.synchronize()
+    assert tail_untouched(dx), "pool2_bwd: wrote past the end of dx"
+    dv = dx[:Hh * Ww * Cs]
+    assert torch.all(dv.view(Hh, Ww, Cs)[:, :, Cc:] == 0), "pad channels must be written as zeros"
+    return from_nhwc(dv, Cc, Hh, Ww)
