@@ -338,3 +338,251 @@ extern "C" int dip_counter_add_n(uint64_t* counters, int n, uint64_t inc, void* 
     DIP_CHECK_LAUNCH();
     return 0;
 }
+
+// ---------------------------------------------------------------- fused super-resolution tail
+// The tail of the super-resolution closure (super-resolution.ipynb:169-186 of the reference: out_LR = downsampler(out_HR);
+// mse(out_LR, img_LR)) in two launches.  The arithmetic of every element is that of the kernels it replaces
+// (lanczos_fwd_kernel / lanczos_bwd_kernel / head_bwd_kernel, misc_kernels.hip): same fmaf chains in the same order, so y and
+// dy are bit-identical to the unfused chain; what differs is how the operands reach the lanes.
+namespace {
+
+constexpr int SR_T = 16;                       // one block = one channel's 16 x 16 tile of LR outputs
+constexpr int SR_LDS_BYTES = 48 * 1024;        // budget of the staged source window
+constexpr int SR_UN = 8;                       // independent global loads per lane while the window is staged
+
+// Forward.  Neighbouring outputs read source windows shifted by f, so the block stages the (15 f + k) columns x ((rp - 1) f + k)
+// rows its outputs read in LDS: row by row, coalesced, clamped once (ReplicationPad2d).  The window is stored PHASE-SPLIT --
+// column x = q f + p lives at p * qn + q -- so the 16 lanes of an output row, which read columns f apart, hit consecutive
+// banks; `pitch` is padded on the host so that the second output row of a 32-lane half lands 16 banks further (ds_read_b32
+// banks modulo 32 per half wave): conflict-free for f = 2, 4, 8.  Taps are wave-uniform: scalar loads (no global store happens
+// before the last of them).  rp < 16 (a window beyond the LDS budget: k = 32, 33 at f = 8) walks the tile in bands of rp rows.
+// K, F: compile-time k, f (0: read from the descriptor).
+template <int K, int F>
+__global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d, const int qn, const int pitch, const int rp) {
+    extern __shared__ float sr_win[];
+    __shared__ float red[256];
+    const int k = K ? K : d.k, f = F ? F : d.f;
+    const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
+    const int ntx = (d.Wo + SR_T - 1) / SR_T, nty = (d.Ho + SR_T - 1) / SR_T;
+    const int b = blockIdx.x;
+    const int ox0 = (b % ntx) * SR_T, oy0 = ((b / ntx) % nty) * SR_T, c = b / (ntx * nty);
+    const float* xc = d.out + (size_t)c * d.H * d.W;
+    const int wc = (SR_T - 1) * f + k, wr = (rp - 1) * f + k, nwin = wr * wc;
+    const int ox = ox0 + lx, oy = oy0 + ly;
+    const bool inside = ox < d.Wo && oy < d.Ho;
+    const int gx0 = ox0 * f - d.pad;
+    float acc = 0.f;
+    for (int ob = 0; ob < SR_T && oy0 + ob < d.Ho; ob += rp) {        // (block-uniform trip count)
+        const int gy0 = (oy0 + ob) * f - d.pad;
+        if (ob) __syncthreads();
+        for (int i0 = tid; i0 < nwin; i0 += 256 * SR_UN) {             // SR_UN loads in flight per lane, then their LDS writes
+            float v[SR_UN];
+#pragma unroll
+            for (int u = 0; u < SR_UN; ++u) {
+                const int idx = i0 + u * 256, wy = idx / wc, wx = idx - wy * wc;
+                v[u] = idx < nwin ? xc[(size_t)min(max(gy0 + wy, 0), d.H - 1) * d.W + min(max(gx0 + wx, 0), d.W - 1)] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < SR_UN; ++u) {
+                const int idx = i0 + u * 256, wy = idx / wc, wx = idx - wy * wc;
+                if (idx < nwin) sr_win[wy * pitch + (wx % f) * qn + wx / f] = v[u];
+            }
+        }
+        __syncthreads();
+        if (inside && ly >= ob && ly < ob + rp) {
+            const float* base = sr_win + (ly - ob) * f * pitch + lx;
+            for (int i = 0; i < k; ++i) {
+                const float* row = base + i * pitch;
+                const float* tp = d.taps + i * k;
+                if constexpr (K > 0) {
+#pragma unroll
+                    for (int j = 0; j < K; ++j) acc = fmaf(tp[j], row[(j % F) * qn + j / F], acc);
+                } else {
+                    for (int jq = 0; jq * f < k; ++jq)
+                        for (int p = 0; p < f && jq * f + p < k; ++p)               // j = jq f + p ascending
+                            acc = fmaf(tp[jq * f + p], row[p * qn + jq], acc);
+                }
+            }
+        }
+    }
+    float sq = 0.f;
+    if (inside) {
+        const size_t o = ((size_t)c * d.Ho + oy) * d.Wo + ox;
+        const float r = acc - d.target[o];
+        d.y[o] = acc;
+        sq = r * r;
+    }
+    red[tid] = sq;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) d.partials[b] = red[0];
+}
+
+// Backward: one lane per HR pixel, every channel (four per float4 store); a block is a 16 x 16 tile of HR pixels.  g is
+// lanczos_bwd_kernel's gather over v = ((y - target) * kk) * gs (at most ceil(k / f)^2 terms off the frame; a frame pixel also
+// takes the padded rows / columns that clamp onto it), then head_bwd_kernel's sigmoid factor and NHWC store with zero pad
+// channels.  STAGE: the few LR pixels the tile's gathers touch -- rows oyb .. oyb + nr - 1, columns oxb .. oxb + ncol - 1 of every
+// channel -- and the taps are formed ONCE per block into LDS (the lanes of a tile read each of them ~ (16 / f + k / f)^2 / 4 times, and
+// y, target would be two loads each time); STAGE = false (a filter whose footprint exceeds the LDS budget) forms v where it
+// is read.
+template <bool STAGE, int K, int F>
+__global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d, const float* __restrict__ gscale,
+                                                          float* __restrict__ dy, const int Cy) {
+    extern __shared__ float sr_lds[];
+    const int HW = d.H * d.W;
+    const int tid = threadIdx.x;
+    const int tx0 = blockIdx.x * SR_T, ty0 = blockIdx.y * SR_T;
+    const int sx = tx0 + (tid & 15), sy = ty0 + (tid >> 4);
+    const int k = K ? K : d.k, f = F ? F : d.f, pad = d.pad, Ho = d.Ho, Wo = d.Wo;
+    float* const sr_tap = sr_lds;                  // [k * k]: a lane's taps depend on its pixel's phase, so not scalar loads
+    float* const sr_v = sr_lds + k * k;
+    const size_t HWo = (size_t)Ho * Wo;
+    const float gs = gscale != nullptr ? *gscale : 1.f;
+    const float kk = 2.f / ((float)d.C * (float)(Ho * Wo));
+    int oyb = 0, oxb = 0, nr = 0, ncol = 0;
+    if constexpr (STAGE) {
+        // padded-domain rows / columns of the whole tile (as ylo .. yhi below, + pad) -> the LR rows / columns they reach
+        const int ty1 = min(ty0 + SR_T - 1, d.H - 1), tx1 = min(tx0 + SR_T - 1, d.W - 1);
+        const int tmin = ty0 == 0 ? 0 : ty0 + pad, tmax = ty1 == d.H - 1 ? d.H - 1 + 2 * pad : ty1 + pad;
+        const int umin = tx0 == 0 ? 0 : tx0 + pad, umax = tx1 == d.W - 1 ? d.W - 1 + 2 * pad : tx1 + pad;
+        oyb = max((tmin - k + 1 + f - 1) / f, 0);
+        oxb = max((umin - k + 1 + f - 1) / f, 0);
+        nr = max(min(tmax / f, Ho - 1) - oyb + 1, 0);
+        ncol = max(min(umax / f, Wo - 1) - oxb + 1, 0);
+        const int per = nr * ncol, n = d.C * per;
+        for (int idx = tid; idx < k * k; idx += 256) sr_tap[idx] = d.taps[idx];
+        for (int idx = tid; idx < n; idx += 256) {
+            const int c = idx / per, rem = idx - c * per, r = rem / ncol, q = rem - r * ncol;
+            const size_t o = (size_t)c * HWo + (size_t)(oyb + r) * Wo + (oxb + q);
+            sr_v[idx] = ((d.y[o] - d.target[o]) * kk) * gs;
+        }
+        __syncthreads();
+    }
+    if (sx >= d.W || sy >= d.H) return;
+    const int p = sy * d.W + sx;
+    const int ylo = (sy == 0) ? -pad : sy, yhi = (sy == d.H - 1) ? d.H - 1 + pad : sy;
+    const int xlo = (sx == 0) ? -pad : sx, xhi = (sx == d.W - 1) ? d.W - 1 + pad : sx;
+    for (int c0 = 0; c0 < Cy; c0 += 4) {
+        const int nc = min(d.C - c0, 4);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (nc > 0) {
+            const float* yc = d.y + (size_t)c0 * HWo;
+            const float* tc = d.target + (size_t)c0 * HWo;
+            const int per = nr * ncol;
+            for (int py = ylo; py <= yhi; ++py) {
+                const int t = py + pad;
+                const int oy_hi = min(t / f, Ho - 1);
+                const int oy_lo = max((t - k + 1 + f - 1) / f, 0);
+                for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+                    const int i = t - oy * f;
+                    if (i < 0 || i >= k) continue;
+                    for (int px = xlo; px <= xhi; ++px) {
+                        const int u = px + pad;
+                        const int ox_hi = min(u / f, Wo - 1);
+                        const int ox_lo = max((u - k + 1 + f - 1) / f, 0);
+                        for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                            const int j = u - ox * f;
+                            if (j < 0 || j >= k) continue;
+                            const float tap = STAGE ? sr_tap[i * k + j] : d.taps[i * k + j];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (e < nc) {
+                                    float v;
+                                    if constexpr (STAGE) {
+                                        v = sr_v[(c0 + e) * per + (oy - oyb) * ncol + (ox - oxb)];
+                                    } else {
+                                        const size_t q = e * HWo + (size_t)oy * Wo + ox;
+                                        v = ((yc[q] - tc[q]) * kk) * gs;
+                                    }
+                                    acc[e] = fmaf(tap, v, acc[e]);
+                                }
+                        }
+                    }
+                }
+            }
+        }
+        f32x4 v4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float g = 0.f;
+            if (e < nc) {
+                g = acc[e];
+                if (d.sigmoid) {
+                    const float o = d.out[(size_t)(c0 + e) * HW + p];
+                    g = g * ((1.f - o) * o);     // aten sigmoid_backward: grad * (1 - y) * y
+                }
+            }
+            v4[e] = g;
+        }
+        *reinterpret_cast<f32x4*>(dy + (size_t)p * Cy + c0) = v4;
+    }
+}
+
+// everything the two entry points refuse before a launch
+const char* sr_loss_refusal(const DipSRLossDesc* dp) {
+    if (dp == nullptr) return "sr_loss: NULL descriptor";
+    const DipSRLossDesc& d = *dp;
+    if (d.out == nullptr || d.taps == nullptr || d.target == nullptr || d.y == nullptr || d.partials == nullptr || d.loss == nullptr)
+        return "sr_loss: NULL field";
+    if (d.C < 1 || d.k < 1 || d.f < 1) return "sr_loss: C, k, f must be >= 1";
+    if (d.H < 1 || d.W < 1 || d.pad < 0 || d.H + 2 * d.pad < d.k || d.W + 2 * d.pad < d.k)
+        return "sr_loss: the padded image is smaller than the filter";
+    if (d.Ho != (d.H + 2 * d.pad - d.k) / d.f + 1 || d.Wo != (d.W + 2 * d.pad - d.k) / d.f + 1)
+        return "sr_loss: Ho / Wo must be (H + 2 pad - k) / f + 1";
+    if ((long long)d.C * d.H * d.W > 0x7fffffffLL) return "sr_loss: image too large";
+    if (d.nblk != dip_sr_loss_nblk(d.C, d.Ho, d.Wo)) return "sr_loss: nblk must come from dip_sr_loss_nblk";
+    if (dip_group_ctx()->ninst > 1) return "sr_loss: grouped launches are not implemented";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int dip_sr_loss_nblk(int C, int Ho, int Wo) {
+    if (C < 1 || Ho < 1 || Wo < 1) return 0;
+    return C * dip_cdiv(Ho, SR_T) * dip_cdiv(Wo, SR_T);
+}
+
+extern "C" int dip_sr_loss_fwd(const DipSRLossDesc* dp, void* stream) {
+    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
+    const DipSRLossDesc& d = *dp;
+    // the phase-split window: qn columns per phase; pitch >= f qn with f * pitch = 16 (mod 32) where one exists (see the kernel)
+    const int wc = (SR_T - 1) * d.f + d.k;
+    const int qn = dip_cdiv(wc, d.f);
+    int pitch = d.f * qn;
+    for (int e = 0; e < 32; ++e)
+        if ((d.f * (pitch + e)) % 32 == 16) { pitch += e; break; }
+    int rp = SR_T;
+    while (rp > 1 && (size_t)((rp - 1) * d.f + d.k) * pitch * 4 > (size_t)SR_LDS_BYTES) rp >>= 1;
+    const size_t lds = (size_t)((rp - 1) * d.f + d.k) * pitch * 4;
+    if (lds > (size_t)SR_LDS_BYTES) DIP_FAIL("sr_loss: the filter's source window does not fit the LDS budget");
+    hipStream_t st = (hipStream_t)stream;
+    if (d.k == 16 && d.f == 4) sr_loss_fwd_kernel<16, 4><<<dim3(d.nblk), dim3(256), lds, st>>>(d, qn, pitch, rp);
+    else sr_loss_fwd_kernel<0, 0><<<dim3(d.nblk), dim3(256), lds, st>>>(d, qn, pitch, rp);
+    DIP_CHECK_LAUNCH();
+    loss_reduce_kernel<false><<<dim3(1), dim3(256), 0, st>>>((const float*)d.partials, d.nblk,
+                                                              1.0 / ((double)d.C * (double)d.Ho * (double)d.Wo), d.loss, DipNoGrp{});
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_sr_loss_bwd(const DipSRLossDesc* dp, const float* gscale, float* dy, int Cy, void* stream) {
+    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
+    const DipSRLossDesc& d = *dp;
+    if (dy == nullptr) DIP_FAIL("sr_loss_bwd: NULL dy");
+    if (Cy < d.C || (Cy & 3)) DIP_FAIL("sr_loss_bwd: Cy must be a multiple of 4 covering C");
+    if ((long long)d.H * d.W * Cy > 0x7fffffffLL) DIP_FAIL("sr_loss_bwd: image too large");
+    // LR rows (columns) a 16-row tile of HR pixels can reach: its padded-domain span is at most 15 + 2 pad (a tile that
+    // touches both edges), and floor(tmax / f) - ceil((tmin - k + 1) / f) + 1 <= (tmax - tmin + k - 1) / f + 1 (+ 1 to spare)
+    const long long nl = (SR_T - 1 + 2 * d.pad + d.k - 1) / d.f + 2;
+    const long long lds = ((long long)d.C * nl * nl + (long long)d.k * d.k) * 4;
+    const dim3 grid(dip_cdiv(d.W, SR_T), dip_cdiv(d.H, SR_T));
+    hipStream_t st = (hipStream_t)stream;
+    if (lds > SR_LDS_BYTES) sr_loss_bwd_kernel<false, 0, 0><<<grid, dim3(256), 0, st>>>(d, gscale, dy, Cy);
+    else if (d.k == 16 && d.f == 4) sr_loss_bwd_kernel<true, 16, 4><<<grid, dim3(256), (size_t)lds, st>>>(d, gscale, dy, Cy);
+    else sr_loss_bwd_kernel<true, 0, 0><<<grid, dim3(256), (size_t)lds, st>>>(d, gscale, dy, Cy);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}

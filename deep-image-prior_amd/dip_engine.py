@@ -1238,8 +1238,8 @@ class SkipEngine:
             return self._run_backward_two_streams(self.bwd_ops, main, compile_only)
         return self._issue(self.bwd_ops, main, "bwd1", compile_only=compile_only)
 
-    def iteration_lists(self):
-        """(forward list without the output conv, backward list) of the current plan as the compiled command lists an eager
+    def iteration_lists(self, with_out_conv=False):
+        """(forward list without the output conv -- with_out_conv: with it --, backward list) of the current plan as the compiled command lists an eager
         closure with the fused loss head issues -- the same objects, so a caller that chains them (dip_optim.NativeIteration:
         one dip_iter_run call per iteration) launches exactly what forward(x, head) + backward() launch.  They live until
         _build_plan resets self._clists; a caller must not keep them beyond that (compare `self._clists` by identity)."""
@@ -1249,7 +1249,7 @@ class SkipEngine:
             raise RuntimeError("dip-amd: DIP_KNOCKOUT is a timing experiment of the eager path; the native iteration refuses it")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("dip-amd: the native iteration is an eager form; hipGraph capture goes through GraphedIteration")
-        return self._launch_forward(None, None, False, compile_only=True), self._launch_backward(None, compile_only=True)
+        return self._launch_forward(None, None, with_out_conv, compile_only=True), self._launch_backward(None, compile_only=True)
 
     def _net_cin(self) -> int:
         return self.sc[0].down_a.Cin
@@ -1271,7 +1271,8 @@ class SkipEngine:
     def forward(self, x: torch.Tensor, head=None):
         """Runs the forward launch list.  head = None: returns the network output [1,C,H,W].
         head = a utils.loss_head.MSEHead: the output conv + sigmoid + (mask) + MSE run as ONE launch
-        (dip_loss_head_fwd) and (loss, out) is returned."""
+        (dip_loss_head_fwd) and (loss, out) is returned; a utils.loss_head.SRHead: the whole net, then the down-sampler +
+        MSE (dip_sr_loss_fwd).  The head says what it launches (fwd_launches / bwd_launches)."""
         if x.dim() != 4 or x.shape[0] != 1:
             raise NotImplementedError("dip-amd: input must be [1,C,H,W] (train-mode BatchNorm couples a batch; "
                                       "independent images run as independent nets)")
@@ -1290,7 +1291,7 @@ class SkipEngine:
                 xs = xs.float()
             xs = xs.contiguous()
             self.fwd_id += 1
-            self._launch_forward(xs.data_ptr(), main, head is None)
+            self._launch_forward(xs.data_ptr(), main, head is None or head.with_out_conv)
             Ho_, Wo_ = self.Hout, self.Wout
             out = torch.empty((1, self.n_out, Ho_, Wo_), dtype=torch.float32, device=dev)
             loss = None
@@ -1300,7 +1301,8 @@ class SkipEngine:
             else:
                 loss = torch.empty((), dtype=torch.float32, device=dev)
                 self._head_desc = head._descriptor(self, out, loss)
-                N.check(lib.dip_loss_head_fwd(C.byref(self._head_desc), stream), "loss_head_fwd")
+                for fn, args, name in head.fwd_launches(self, self._head_desc):
+                    N.check(fn(*args, stream), name)
             if len(self.bns):
                 self.nbt.add_(1)
         # (aliases without autograd history: holding the Function's own output tensors would keep the
@@ -1353,8 +1355,8 @@ class SkipEngine:
                 if gl.dtype != torch.float32:
                     gl = gl.float()
                 self._gloss_keep = gl
-                N.check(lib.dip_loss_head_bwd(C.byref(self._head_desc), gl.data_ptr(), _ptr(self.dy_out),
-                                              round_up(self.n_out, 4), stream), "loss_head_bwd")
+                for fn, args, name in self.last_head.bwd_launches(self, self._head_desc, gl.data_ptr()):
+                    N.check(fn(*args, stream), name)
             self._launch_backward(main)
             gx = None
             if need_input_grad:
@@ -1588,7 +1590,7 @@ class _SkipFn(torch.autograd.Function):
 
 
 class _SkipLossFn(torch.autograd.Function):
-    """net + fused loss head (utils/loss_head.MSEHead): returns (loss, out); `out` is not differentiable."""
+    """net + fused loss head (utils/loss_head.MSEHead / SRHead): returns (loss, out); `out` is not differentiable."""
 
     @staticmethod
     def forward(ctx, engine: SkipEngine, head, x, *params):

@@ -105,6 +105,13 @@ class DipLossHeadDesc(C.Structure):
                 ("out", C.c_void_p), ("partials", C.c_void_p), ("nblk", C.c_int32), ("loss", C.c_void_p)]
 
 
+class DipSRLossDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("taps", C.c_void_p), ("target", C.c_void_p), ("y", C.c_void_p),
+                ("partials", C.c_void_p), ("nblk", C.c_int32), ("loss", C.c_void_p),
+                ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("k", C.c_int32), ("f", C.c_int32),
+                ("pad", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("sigmoid", C.c_int32)]
+
+
 class DipFitMonitorDesc(C.Structure):
     _fields_ = [("out", C.c_void_p), ("noisy", C.c_void_p), ("gt", C.c_void_p), ("out_avg", C.c_void_p), ("n", C.c_int64),
                 ("exp_weight", C.c_float), ("backtrack_db", C.c_float), ("loss", C.c_void_p), ("partial", C.c_void_p),
@@ -245,6 +252,9 @@ _SIGS = {
     "dip_loss_head_nblk": (C.c_int, [C.c_int, C.c_int]),
     "dip_loss_head_fwd": (C.c_int, [C.POINTER(DipLossHeadDesc), C.c_void_p]),
     "dip_loss_head_bwd": (C.c_int, [C.POINTER(DipLossHeadDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dip_sr_loss_nblk": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "dip_sr_loss_fwd": (C.c_int, [C.POINTER(DipSRLossDesc), C.c_void_p]),
+    "dip_sr_loss_bwd": (C.c_int, [C.POINTER(DipSRLossDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dip_fit_monitor_nblk": (C.c_int, [C.c_int64]),
     "dip_fit_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),

@@ -13,7 +13,7 @@ hipGraph and replays it.  Several independent fits: `GraphedIteration.group(dip_
 captures ONE launch list that serves all of them (every kernel launch covers all instances), and
 `GraphedIteration.group([(optimizer, closure), ...])` -- arbitrary closures -- one graph per fit on its own stream.
 
-`NativeIteration` is the eager form without autograd: head (utils.loss_head.MSEHead), reg-noise (utils.reg_noise.RegNoise) and
+`NativeIteration` is the eager form without autograd: head (utils.loss_head.MSEHead or SRHead), reg-noise (utils.reg_noise.RegNoise) and
 optimiser known statically, the whole iteration -- noise, forward list, loss head, backward list, Adam -- is ONE call into
 the library (dip_iter_run), bit-identical to {zero_grad(); closure(); step()} and interchangeable with it at any iteration.
 With monitor=utils.fit_monitor.FitMonitor(...) the same call also does the closure's bookkeeping (EMA, PSNRs, back-tracking).
@@ -335,12 +335,16 @@ class NativeIteration:
         it.run(show_every); print(monitor.last())     # the notebook's print loop
         monitor.history(); monitor.out_avg
 
+    head = SRHead(net, img_LR, downsampler) (super-resolution.ipynb:169-186) takes the MSEHead's place: the forward list then
+    runs WITH the output conv and the head's launches are dip_head_fwd + dip_sr_loss_fwd and dip_sr_loss_bwd; `it.out` is
+    out_HR, `head.out_LR` the down-sampled output.
+
     step() / run(n) past the monitor's capacity raise before anything is issued.  The monitor's buffers and settings are
     part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt)."""
 
     def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None):
         import dip_group
-        from utils.loss_head import MSEHead
+        from utils.loss_head import MSEHead, SRHead
         from utils.reg_noise import RegNoise
         if isinstance(net, dip_group.GroupedFits) or isinstance(head, dip_group.GroupedFits):
             raise NotImplementedError("dip-amd: NativeIteration drives ONE fit; grouped fits run through "
@@ -371,10 +375,11 @@ class NativeIteration:
                              f"{tuple(net_input.shape)}")
         if net_input.requires_grad:
             raise ValueError("dip-amd: net_input requires grad (opt_over='net,input'): that goes through the eager closure")
-        if not isinstance(head, MSEHead):
-            raise TypeError(f"dip-amd: NativeIteration needs a utils.loss_head.MSEHead, got {type(head).__name__}")
+        if not isinstance(head, (MSEHead, SRHead)):
+            raise TypeError(f"dip-amd: NativeIteration needs a utils.loss_head.MSEHead or SRHead, got {type(head).__name__}")
         if head.net is not net:
-            raise ValueError("dip-amd: the MSEHead was built for another net")
+            raise ValueError(f"dip-amd: the {type(head).__name__} was built for another net")
+        head._check_state()
         if reg_noise is not None:
             if not isinstance(reg_noise, RegNoise):
                 raise TypeError("dip-amd: reg_noise must be a utils.reg_noise.RegNoise or None, got "
@@ -420,7 +425,7 @@ class NativeIteration:
         # (an engine that has never planned has no op lists yet: None never equals a built key)
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
                 opt.lr, opt.betas, opt.eps, id(opt._groups),
-                id(head.target), head.target.data_ptr(), id(head.mask), head.mask_c,
+                head._plan_key(),
                 None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
             + (() if m is None else ((id(m), id(m.records), id(m.state), id(m.out_avg), id(m.partial), id(m.snapshot),
                                       id(m.counter), m.exp_weight, m.show_every, m.backtrack_db, id(m.noisy), id(m.gt),
@@ -437,7 +442,7 @@ class NativeIteration:
         eng._prepare(dev, H, W, Cimg)
         if opt._sig != opt._signature():
             opt._prepare()
-        fwd, bwd = eng.iteration_lists()
+        fwd, bwd = eng.iteration_lists(with_out_conv=head.with_out_conv)
         out = self.out
         if out is None or tuple(out.shape) != (1, eng.n_out, eng.Hout, eng.Wout) or out.device != dev:
             out = torch.empty((1, eng.n_out, eng.Hout, eng.Wout), dtype=torch.float32, device=dev)
@@ -450,11 +455,10 @@ class NativeIteration:
             pre.append((lib.dip_noise_axpy_dev, (reg.saved.data_ptr(), reg.out.data_ptr(), reg.saved.numel(), reg.std,
                                                  reg.seed, reg.offset.data_ptr()), "noise_axpy_dev"))
         pre += eng._forward_prologue(x.data_ptr())
-        mid = [(lib.dip_loss_head_fwd, (C.byref(desc),), "loss_head_fwd")]
+        mid = head.fwd_launches(eng, desc)
         if len(eng.bns):
             mid.append((lib.dip_counter_add_n, (eng.nbt.data_ptr(), eng.nbt.numel(), 1), "num_batches_tracked"))
-        mid.append((lib.dip_loss_head_bwd, (C.byref(desc), self._one.data_ptr(), eng.dy_out.data_ptr(),
-                                            N.round_up(eng.n_out, 4)), "loss_head_bwd"))
+        mid += head.bwd_launches(eng, desc, self._one.data_ptr())
         st = opt._state(dev, opt.step_count)
         b1, b2 = float(opt.betas[0]), float(opt.betas[1])
         adam = [(lib.dip_adam_tick, (st.data_ptr(), float(opt.lr), b1, b2), "adam_tick")]
@@ -483,8 +487,8 @@ class NativeIteration:
         views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]
         self.out = out
         # everything a slot points to stays alive with the plan, and so does every object whose id is part of the key
-        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, views=views, x=x, state=st, loss0=loss0, scratch=head._scratch,
-                          keep=(head.target, head.mask, head._keep, eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
+        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, views=views, x=x, state=st, loss0=loss0,
+                          keep=(head._plan_keep(), eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
                                 None if reg is None else (reg.saved, reg.out, reg.offset),
                                 None if m is None else (m, m.records, m.state, m.out_avg, m.partial, m.snapshot, m.counter,
@@ -496,6 +500,7 @@ class NativeIteration:
         self._check_training()
         self._check_capture()
         self._check_monitor()                     # (`it.monitor` may have been replaced)
+        self.head._check_state()                  # (an SRHead's down-sampler may have become trainable)
         m = self.monitor
         if m is not None and m.i + n > m.capacity:
             raise RuntimeError(f"dip-amd: FitMonitor capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
@@ -512,7 +517,7 @@ class NativeIteration:
         return ptrs
 
     def _issue(self, loss_ptr, ptrs):
-        self._plan["desc"].loss = loss_ptr        # read by dip_loss_head_fwd when it launches
+        self._plan["desc"].loss = loss_ptr        # read by the head's forward launch (dip_loss_head_fwd / dip_sr_loss_fwd)
         if self._plan["mdesc"] is not None:
             self._plan["mdesc"].loss = loss_ptr   # column 0 of this iteration's record (read by dip_fit_monitor_dev)
         self._plan["lists"].run(ptrs)

@@ -15,6 +15,23 @@ the same arithmetic out as separate PyTorch ops in every closure):
 LDS tree per block and a fixed-order fp64 sum of the per-block partials; `backward()` starts from
 dip_loss_head_bwd.  The plain `out = net(x); mse(out, t)` spelling keeps working (the head,
 the mask product and the MSE then run as separate kernels); this class is the opt-in fused path.
+
+Super-resolution (super-resolution.ipynb:169-186 of the reference):
+
+    out_HR = net(net_input); out_LR = downsampler(out_HR); total_loss = mse(out_LR, img_LR_var)
+
+    head = SRHead(net, img_LR_var, downsampler)
+    def closure():
+        total_loss, out_HR = head(net_input)                  # head.out_LR: the down-sampled output, for psnr_LR
+        total_loss.backward()
+        return total_loss
+
+`SRHead` runs the whole net (out_HR is bit-identical to net(net_input)) and then ONE launch for the Lanczos down-sampler +
+MSE (dip_sr_loss_fwd); `backward()` starts from dip_sr_loss_bwd (MSE backward + the down-sampler's adjoint + the sigmoid
+factor) instead of three autograd nodes.
+
+Both heads describe their launches ONCE, as the (fn, args, name) triples SkipEngine.forward / backward issue one by one and
+dip_optim.NativeIteration compiles into its command arrays: `with_out_conv`, `_descriptor`, `fwd_launches`, `bwd_launches`.
 """
 import ctypes as C
 
@@ -24,6 +41,9 @@ import dip_native as N
 
 
 class MSEHead:
+    kind = "mse"
+    with_out_conv = False       # dip_loss_head_fwd runs the output conv itself: the forward list stops in front of it
+
     def __init__(self, net, target, mask=None):
         eng = getattr(net, "__dict__", {}).get("_dip_engine")
         if eng is None or isinstance(eng, Exception):
@@ -68,6 +88,126 @@ class MSEHead:
                                  ptr(eng.params, oc.b_off) if oc.b_off >= 0 else None, oc.Cout, H * W,
                                  1 if eng.need_sigmoid else 0, ptr(self.target), ptr(self.mask), self.mask_c,
                                  ptr(out), ptr(partials), nblk, ptr(loss))
+
+    def fwd_launches(self, eng, desc):
+        """The head's forward as (fn, args, name) triples; args without the trailing stream."""
+        return [(eng.lib.dip_loss_head_fwd, (C.byref(desc),), "loss_head_fwd")]
+
+    def bwd_launches(self, eng, desc, gscale_ptr):
+        """What writes eng.dy_out (the gradient wrt the output conv's result) from d loss at gscale_ptr."""
+        return [(eng.lib.dip_loss_head_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
+                 "loss_head_bwd")]
+
+    def _check_state(self):
+        pass
+
+    def _plan_key(self):
+        """What a compiled command array (dip_optim.NativeIteration) was built from, objects by identity."""
+        return (self.kind, id(self.target), self.target.data_ptr(), id(self.mask), self.mask_c)
+
+    def _plan_keep(self):
+        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
+        return (self.target, self.mask, self._keep, self._scratch)
+
+    def __call__(self, net_input):
+        import dip_engine
+        if not self.net.training:
+            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented")
+        loss, out = dip_engine.run_net_loss(self.engine, self, net_input)
+        return loss, out
+
+
+class SRHead:
+    """net + fixed-taps Downsampler + MSE (see the module docstring).  `target` (img_LR) may be replaced and the
+    down-sampler's state reloaded between calls; `out_LR` is a buffer this object owns and overwrites."""
+    kind = "sr"
+    with_out_conv = True        # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
+
+    def __init__(self, net, img_LR, downsampler):
+        from models.downsampler import Downsampler
+        eng = getattr(net, "__dict__", {}).get("_dip_engine")
+        if eng is None or isinstance(eng, Exception):
+            raise RuntimeError("dip-amd: SRHead needs a net built by models.skip.skip()")
+        if eng.kind != "skip":
+            raise NotImplementedError("dip-amd: SRHead covers skip() nets; the ResNet backbone has no fused loss head")
+        if not isinstance(downsampler, Downsampler):
+            raise TypeError(f"dip-amd: SRHead needs a models.downsampler.Downsampler, got {type(downsampler).__name__}")
+        self.net, self.engine, self.downsampler = net, eng, downsampler
+        self._check_state()
+        n_out = eng.out_conv.Cout
+        if downsampler.downsampler_.weight.shape[0] != n_out:
+            raise ValueError(f"SRHead: the Downsampler has {downsampler.downsampler_.weight.shape[0]} planes, the net output "
+                             f"has {n_out}")
+        if not isinstance(img_LR, torch.Tensor) or img_LR.dim() != 4 or img_LR.shape[0] != 1 or img_LR.shape[1] != n_out:
+            raise ValueError(f"SRHead: img_LR must be [1,{n_out},Ho,Wo], got {tuple(getattr(img_LR, 'shape', ()))}")
+        if not img_LR.is_cuda:
+            raise RuntimeError("dip-amd: SRHead works on MI355X tensors only (no CPU fallback)")
+        self.target = img_LR.detach().contiguous().float()
+        self._scratch = None
+        self._y = None
+        self._keep = None
+
+    def _check_state(self):
+        """The fused tail applies the FIXED taps: a down-sampler that is (or may be) trained is refused at every call."""
+        d = self.downsampler
+        if getattr(d, "_dense", False) or getattr(d, "_nondiag", False) or d.downsampler_.weight.requires_grad \
+                or d.downsampler_.bias.requires_grad:
+            raise NotImplementedError("dip-amd: SRHead covers the fixed-taps Downsampler; a trainable one (opt_over='down', a "
+                                      "loaded non-diagonal weight, or the down-sampler of a skip() net) goes through the "
+                                      "spelled closure: out_LR = downsampler(net(x)); mse(out_LR, img_LR)")
+
+    @property
+    def out_LR(self):
+        """downsampler(out_HR) of the last call, [1,C,Ho,Wo] (overwritten by the next one)."""
+        return self._y
+
+    def _geometry(self, eng):
+        d = self.downsampler
+        k, f, pad = int(d.kernel.shape[0]), int(d.factor), int(d._pad)
+        H, W = eng.Hout, eng.Wout
+        if H + 2 * pad < k or W + 2 * pad < k:
+            raise ValueError(f"SRHead: the net output {(H, W)} is smaller than the {k}x{k} filter")
+        return k, f, pad, (H + 2 * pad - k) // f + 1, (W + 2 * pad - k) // f + 1
+
+    def _descriptor(self, eng, out, loss):
+        """DipSRLossDesc for the engine's current plan (called by SkipEngine.forward and NativeIteration)."""
+        self._check_state()
+        k, f, pad, Ho, Wo = self._geometry(eng)
+        if tuple(self.target.shape[2:]) != (Ho, Wo):
+            raise ValueError(f"SRHead: img_LR is {tuple(self.target.shape[2:])}, the down-sampled net output is {(Ho, Wo)}")
+        dev = out.device
+        taps = self.downsampler._taps
+        if taps.device != dev or self.target.device != dev:
+            raise RuntimeError(f"dip-amd: SRHead: the Downsampler is on {taps.device}, img_LR on {self.target.device}, the net "
+                               f"runs on {dev}")
+        Cn = eng.n_out
+        nblk = eng.lib.dip_sr_loss_nblk(Cn, Ho, Wo)
+        if self._scratch is None or self._scratch.numel() != nblk or self._scratch.device != dev:
+            self._scratch = torch.empty(nblk, dtype=torch.float32, device=dev)
+        if self._y is None or tuple(self._y.shape) != (1, Cn, Ho, Wo) or self._y.device != dev:
+            self._y = torch.empty((1, Cn, Ho, Wo), dtype=torch.float32, device=dev)
+        self._keep = (out.detach(), taps)
+        return N.DipSRLossDesc(out.data_ptr(), taps.data_ptr(), self.target.data_ptr(), self._y.data_ptr(),
+                               self._scratch.data_ptr(), nblk, loss.data_ptr(), Cn, eng.Hout, eng.Wout, k, f, pad, Ho, Wo,
+                               1 if eng.need_sigmoid else 0)
+
+    def fwd_launches(self, eng, desc):
+        Cs = N.round_up(eng.n_out, 4)
+        return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.out, eng.n_out, eng.Hout * eng.Wout, Cs,
+                                        1 if eng.need_sigmoid else 0), "head_fwd"),
+                (eng.lib.dip_sr_loss_fwd, (C.byref(desc),), "sr_loss_fwd")]
+
+    def bwd_launches(self, eng, desc, gscale_ptr):
+        return [(eng.lib.dip_sr_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
+                 "sr_loss_bwd")]
+
+    def _plan_key(self):
+        d = self.downsampler
+        return (self.kind, id(self.target), self.target.data_ptr(), id(d), id(d._taps), int(d.kernel.shape[0]), int(d.factor),
+                int(d._pad), id(self._y))
+
+    def _plan_keep(self):
+        return (self.target, self.downsampler, self._keep, self._scratch, self._y)
 
     def __call__(self, net_input):
         import dip_engine

@@ -623,6 +623,33 @@ int dip_loss_head_nblk(int HW, int Cin);
 int dip_loss_head_fwd(const DipLossHeadDesc* d, void* stream);
 int dip_loss_head_bwd(const DipLossHeadDesc* d, const float* gscale, float* dy, int Cy, void* stream);
 
+/* ---------------------------------------------------------------- fused super-resolution tail ---- */
+/* The tail of the super-resolution closure (super-resolution.ipynb:169-186: out_LR = downsampler(out_HR);
+ * total_loss = mse(out_LR, img_LR_var)) behind dip_head_fwd, in two launches: the fixed-taps Downsampler
+ * (models/downsampler.py:65-71: ReplicationPad2d(pad) + depth-wise k x k stride-f correlation) + torch.nn.MSELoss.
+ *   forward : y[c][oy][ox] = the fmaf chain of dip_lanczos_down_fwd (taps row-major, source index clamped, from 0.f), so y is
+ *             bit-identical to dip_lanczos_down_fwd(out);  r = y - target;  one fp32 partial of sum r^2 per block, then the
+ *             fixed-order fp64 sum of dip_loss_head_fwd with scale 1/(C*Ho*Wo) in a launch of its own: no float atomics.
+ *   backward: v = ((y - target) * kk) * gs with kk = 2.f / ((float)C * (float)(Ho*Wo)), gs = gscale ? *gscale : 1.f;
+ *             g = the fmaf chain of dip_lanczos_down_bwd over v;  dy[p][c] = sigmoid ? g * ((1.f - out) * out) : g
+ *             (NHWC, channel stride Cy, pad channels zero, as dip_head_bwd): bit-identical to that chain of three.
+ * The descriptor is read when the call launches (`loss` may be rewritten by the host between calls).  Refused with -1 before
+ * any launch: a NULL descriptor or field, C, k, f < 1, Ho / Wo != (H + 2 pad - k) / f + 1, nblk != dip_sr_loss_nblk(C, Ho, Wo),
+ * Cy < C or Cy % 4 != 0, a grouped launch.  sizeof(DipSRLossDesc) == 96 (LP64). */
+typedef struct DipSRLossDesc {
+    const float* out;      /* [C][H*W] NCHW: the network output (input here) */
+    const float* taps;     /* [k*k] */
+    const float* target;   /* [C][Ho*Wo] */
+    float* y;              /* [C][Ho*Wo]: the LR output, written by the forward, read by the backward */
+    float* partials;       /* nblk floats */
+    int nblk;              /* dip_sr_loss_nblk(C, Ho, Wo) */
+    float* loss;           /* 1 float */
+    int C, H, W, k, f, pad, Ho, Wo, sigmoid;
+} DipSRLossDesc;
+int dip_sr_loss_nblk(int C, int Ho, int Wo);
+int dip_sr_loss_fwd(const DipSRLossDesc* d, void* stream);
+int dip_sr_loss_bwd(const DipSRLossDesc* d, const float* gscale, float* dy, int Cy, void* stream);
+
 /* ---------------------------------------------------------------- closure bookkeeping ---- */
 /* The per-iteration bookkeeping of the notebooks' closures without host round trips
  * (denoising.ipynb:214-248): EMA of the output, PSNR against the noisy / clean image, and the
