@@ -79,6 +79,9 @@ template <class F> __host__ __device__ inline void dip_ptrs(DipUpcatDesc& d, F& 
 template <class F> __host__ __device__ inline void dip_ptrs(DipLossHeadDesc& d, F& f) {
     f(d.u); dip_ptrs(d.tr, f); f(d.w); f(d.bias); f(d.target); f(d.mask); f(d.out); f(d.partials); f(d.loss);
 }
+template <class F> __host__ __device__ inline void dip_ptrs(DipSRLossDesc& d, F& f) {
+    f(d.out); f(d.taps); f(d.target); f(d.y); f(d.partials); f(d.loss);
+}
 
 struct DipShiftF {
     long long off;

@@ -357,8 +357,10 @@ constexpr int SR_UN = 8;                       // independent global loads per l
 // banks modulo 32 per half wave): conflict-free for f = 2, 4, 8.  Taps are wave-uniform: scalar loads (no global store happens
 // before the last of them).  rp < 16 (a window beyond the LDS budget: k = 32, 33 at f = 8) walks the tile in bands of rp rows.
 // K, F: compile-time k, f (0: read from the descriptor).
-template <int K, int F>
-__global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d, const int qn, const int pitch, const int rp) {
+template <int K, int F, bool GRP = false>
+__global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d_, const int qn, const int pitch, const int rp,
+                                                          const DipGrpArg<GRP> grp) {
+    DIP_GRP_DESC(DipSRLossDesc, d);
     extern __shared__ float sr_win[];
     __shared__ float red[256];
     const int k = K ? K : d.k, f = F ? F : d.f;
@@ -428,9 +430,12 @@ __global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d,
 // channel -- and the taps are formed ONCE per block into LDS (the lanes of a tile read each of them ~ (16 / f + k / f)^2 / 4 times, and
 // y, target would be two loads each time); STAGE = false (a filter whose footprint exceeds the LDS budget) forms v where it
 // is read.
-template <bool STAGE, int K, int F>
-__global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d, const float* __restrict__ gscale,
-                                                          float* __restrict__ dy, const int Cy) {
+template <bool STAGE, int K, int F, bool GRP = false>
+__global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d_, const float* __restrict__ gscale_,
+                                                          float* __restrict__ dy_, const int Cy, const DipGrpArg<GRP> grp) {
+    DIP_GRP_DESC(DipSRLossDesc, d);
+    DIP_GRP_PTR(const float*, gscale);
+    DIP_GRP_PTR(float*, dy);
     extern __shared__ float sr_lds[];
     const int HW = d.H * d.W;
     const int tid = threadIdx.x;
@@ -534,7 +539,6 @@ const char* sr_loss_refusal(const DipSRLossDesc* dp) {
         return "sr_loss: Ho / Wo must be (H + 2 pad - k) / f + 1";
     if ((long long)d.C * d.H * d.W > 0x7fffffffLL) return "sr_loss: image too large";
     if (d.nblk != dip_sr_loss_nblk(d.C, d.Ho, d.Wo)) return "sr_loss: nblk must come from dip_sr_loss_nblk";
-    if (dip_group_ctx()->ninst > 1) return "sr_loss: grouped launches are not implemented";
     return nullptr;
 }
 
@@ -559,11 +563,15 @@ extern "C" int dip_sr_loss_fwd(const DipSRLossDesc* dp, void* stream) {
     const size_t lds = (size_t)((rp - 1) * d.f + d.k) * pitch * 4;
     if (lds > (size_t)SR_LDS_BYTES) DIP_FAIL("sr_loss: the filter's source window does not fit the LDS budget");
     hipStream_t st = (hipStream_t)stream;
-    if (d.k == 16 && d.f == 4) sr_loss_fwd_kernel<16, 4><<<dim3(d.nblk), dim3(256), lds, st>>>(d, qn, pitch, rp);
-    else sr_loss_fwd_kernel<0, 0><<<dim3(d.nblk), dim3(256), lds, st>>>(d, qn, pitch, rp);
+    const dim3 grid(d.nblk), blk(256);
+    if (d.k == 16 && d.f == 4)
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_fwd_kernel<16, 4>, sr_loss_fwd_kernel<16, 4, true>, grid, blk, lds, st, d, qn, pitch, rp);
+    else
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_fwd_kernel<0, 0>, sr_loss_fwd_kernel<0, 0, true>, grid, blk, lds, st, d, qn, pitch, rp);
     DIP_CHECK_LAUNCH();
-    loss_reduce_kernel<false><<<dim3(1), dim3(256), 0, st>>>((const float*)d.partials, d.nblk,
-                                                              1.0 / ((double)d.C * (double)d.Ho * (double)d.Wo), d.loss, DipNoGrp{});
+    // (through the pair as well: launched bare it would reduce instance 0 only)
+    dip_launch_pair<DIP_FAM_LOSS>(loss_reduce_kernel<false>, loss_reduce_kernel<true>, dim3(1), blk, 0, st, (const float*)d.partials,
+                                  d.nblk, 1.0 / ((double)d.C * (double)d.Ho * (double)d.Wo), d.loss);
     DIP_CHECK_LAUNCH();
     return 0;
 }
@@ -580,9 +588,16 @@ extern "C" int dip_sr_loss_bwd(const DipSRLossDesc* dp, const float* gscale, flo
     const long long lds = ((long long)d.C * nl * nl + (long long)d.k * d.k) * 4;
     const dim3 grid(dip_cdiv(d.W, SR_T), dip_cdiv(d.H, SR_T));
     hipStream_t st = (hipStream_t)stream;
-    if (lds > SR_LDS_BYTES) sr_loss_bwd_kernel<false, 0, 0><<<grid, dim3(256), 0, st>>>(d, gscale, dy, Cy);
-    else if (d.k == 16 && d.f == 4) sr_loss_bwd_kernel<true, 16, 4><<<grid, dim3(256), (size_t)lds, st>>>(d, gscale, dy, Cy);
-    else sr_loss_bwd_kernel<true, 0, 0><<<grid, dim3(256), (size_t)lds, st>>>(d, gscale, dy, Cy);
+    const dim3 blk(256);
+    if (lds > SR_LDS_BYTES)
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<false, 0, 0>, sr_loss_bwd_kernel<false, 0, 0, true>, grid, blk, 0, st,
+                                      d, gscale, dy, Cy);
+    else if (d.k == 16 && d.f == 4)
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 16, 4>, sr_loss_bwd_kernel<true, 16, 4, true>, grid, blk, (size_t)lds,
+                                      st, d, gscale, dy, Cy);
+    else
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 0, 0>, sr_loss_bwd_kernel<true, 0, 0, true>, grid, blk, (size_t)lds,
+                                      st, d, gscale, dy, Cy);
     DIP_CHECK_LAUNCH();
     return 0;
 }

@@ -67,8 +67,11 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ y, float* __restrict__ out, int C,
-                                                       int HW, int Cs, int sigmoid) {
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ y_, float* __restrict__ out_, int C,
+                                                       int HW, int Cs, int sigmoid, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float*, y);
+    DIP_GRP_PTR(float*, out);
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
     for (int c = 0; c < C; c += 4) {
@@ -398,7 +401,8 @@ extern "C" int dip_nhwc_to_nchw(const float* src, float* dst, int C, int HW, int
     return 0;
 }
 extern "C" int dip_head_fwd(const float* y, float* out, int C, int HW, int Cs, int sigmoid, void* stream) {
-    dip_launch(head_fwd_kernel, dim3(dip_cdiv(HW, 256)), dim3(256), 0, (hipStream_t)stream, y, out, C, HW, Cs, sigmoid);
+    dip_launch_pair<DIP_FAM_MISC>(head_fwd_kernel<false>, head_fwd_kernel<true>, dim3(dip_cdiv(HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                                  y, out, C, HW, Cs, sigmoid);
     DIP_CHECK_LAUNCH();
     return 0;
 }

@@ -21,6 +21,15 @@ is bit-identical to the same fit run on its own (tests/test_group_gpu.py).
     g.out, g.out_avg                # [B, C, H, W]: network outputs / their exponential moving averages
     nets[b].state_dict()            # the parameters of nets[b] are views of its slab: always current
 
+Super-resolution (super-resolution.ipynb:169-186 of the reference; the batches of super-resolution_eval_script.py and the arms
+of sr_prior_effect.ipynb): `downsamplers=[...]`, one fixed-taps models.downsampler.Downsampler per instance, switches the
+tail of every instance to the one of utils.loss_head.SRHead -- the whole net, dip_head_fwd, dip_sr_loss_fwd, dip_sr_loss_bwd
+-- with `targets` the LR images.  The taps are per-instance data of the slab like the targets, so the instances may use
+different taps of one (k, factor, pad); there is no mask.
+
+    g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, reg_noise_std=0.03)
+    g.out, g.out_LR                 # [B, C, H, W] HR outputs, [B, C, Ho, Wo] their down-sampled versions
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -70,14 +79,17 @@ class GroupedFits:
     ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
-                 ema_init="first", device=None, _dry_cpu=False):
+                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
-        ema_init 'first' = out_avg starts as the first output (denoising.ipynb:214-215), 'zeros' = starts at 0."""
+        ema_init 'first' = out_avg starts as the first output (denoising.ipynb:214-215), 'zeros' = starts at 0.
+        downsamplers: None = the denoising / inpainting closure; B fixed-taps Downsamplers of one (k, factor, pad) = the
+        super-resolution closure, targets = the LR images [1,C,Ho,Wo], no masks."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
+        self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
             raise RuntimeError("dip-amd: GroupedFits needs nets built by models.skip.skip()")
@@ -122,6 +134,9 @@ class GroupedFits:
             raise NotImplementedError("dip-amd: the fused loss head covers a 1x1 output conv with <= 4 channels")
         if t0.dim() != 4 or t0.shape[0] != 1 or t0.shape[1] != oc.Cout:
             raise ValueError(f"GroupedFits: targets must be [1,{oc.Cout},H,W], got {tuple(t0.shape)}")
+        if self.downsamplers is not None and self.downsamplers[0].downsampler_.weight.shape[0] != oc.Cout:
+            raise ValueError(f"GroupedFits: the Downsamplers have {self.downsamplers[0].downsampler_.weight.shape[0]} planes, "
+                             f"the net output has {oc.Cout}")
         self.mask_c = 0
         m0 = None
         if masks is not None and masks[0] is not None:
@@ -161,6 +176,8 @@ class GroupedFits:
                     self._inst(ex["target"], b).copy_(targets[b].detach().to(device).float().reshape(-1))
                     if ex["mask"] is not None:
                         self._inst(ex["mask"], b).copy_(self._mask4(masks[b]).to(device).float().reshape(-1))
+                    if self.downsamplers is not None:
+                        self._inst(ex["taps"], b).copy_(self.downsamplers[b]._taps.detach().to(device).float().reshape(-1))
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
             # --- what the caller reads: strided views over the instances
             HWo = eng.Hout * eng.Wout
@@ -168,6 +185,10 @@ class GroupedFits:
             self.out = self._strided(ex["out"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1))
             self.out_avg = torch.zeros((B, oc.Cout, eng.Hout, eng.Wout), dtype=torch.float32, device=device) \
                 if self.exp_weight is not None else None
+            self.out_LR = None
+            if self.downsamplers is not None:
+                _, _, _, Ho, Wo = self._sr_geom
+                self.out_LR = self._strided(ex["y"], (B, oc.Cout, Ho, Wo), (Ho * Wo, Wo, 1))
             self._nbt_all = self._strided(eng.nbt, (B, eng.nbt.numel()), (1,))
             if not self._dry:
                 torch.cuda.synchronize(device)
@@ -175,6 +196,28 @@ class GroupedFits:
     # ------------------------------------------------------------------ construction helpers
     def _devctx(self):
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
+
+    @staticmethod
+    def _check_downsamplers(downsamplers, B, masks):
+        """What can be said about `downsamplers` before anything is planned or allocated (the rule of SRHead, per instance)."""
+        from models.downsampler import Downsampler
+        from utils.loss_head import sr_check_fixed_taps, sr_support
+        downs = list(downsamplers)
+        if len(downs) != B:
+            raise ValueError(f"GroupedFits: one Downsampler per instance: got {len(downs)} for {B} nets")
+        if masks is not None:
+            raise ValueError("GroupedFits: masks and downsamplers exclude each other (the super-resolution loss has no mask)")
+        for b, d in enumerate(downs):
+            if not isinstance(d, Downsampler):
+                raise TypeError(f"dip-amd: GroupedFits needs models.downsampler.Downsampler objects, instance {b} is a "
+                                f"{type(d).__name__}")
+            sr_check_fixed_taps(d, who="GroupedFits")
+            if sr_support(d) != sr_support(downs[0]):
+                raise ValueError(f"GroupedFits: the Downsampler of instance {b} has (k, factor, pad) = {sr_support(d)}, "
+                                 f"instance 0 has {sr_support(downs[0])}: one launch list serves one filter support")
+            if d.downsampler_.weight.shape[0] != downs[0].downsampler_.weight.shape[0]:
+                raise ValueError(f"GroupedFits: the Downsampler of instance {b} differs from instance 0 in planes")
+        return downs
 
     def pointers_outside_row0(self):
         """Self-check of the memory model: every device pointer of the launch list (descriptor fields and pointer
@@ -195,7 +238,11 @@ class GroupedFits:
             for fn, args, name in ops:
                 for k, a in enumerate(args):
                     visit(name, f"arg{k}", a._obj if hasattr(a, "_obj") else a)
-        visit("loss_head", "desc", self._head)
+        visit("sr_loss" if self.downsamplers is not None else "loss_head", "desc", self._head)
+        for fn, args, name in self._head_fwd + self._head_bwd:      # pointer ARGUMENTS of the head's launches (y_out, gl, dy_out)
+            for k, a in enumerate(args):
+                if not hasattr(a, "_obj"):
+                    visit(name, f"arg{k}", a)
         for k, t in self._row0_extra.items():
             if t is not None:
                 visit("extra", k, t.data_ptr())
@@ -222,6 +269,8 @@ class GroupedFits:
         if Cimg != eng.sc[0].down_a.Cin:
             raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {eng.sc[0].down_a.Cin}")
         eng._build_plan(H, W, Cimg)
+        if self.downsamplers is not None:
+            return self._build_row0_sr(slab, Cimg, H, W, t0)
         if (eng.Hout, eng.Wout) != tuple(t0.shape[2:]):
             raise ValueError(f"GroupedFits: targets are {tuple(t0.shape[2:])}, the net output is {(eng.Hout, eng.Wout)}")
         oc = eng.out_conv
@@ -251,6 +300,48 @@ class GroupedFits:
                                        ptr(eng.params, oc.b_off) if oc.b_off >= 0 else None, oc.Cout, eng.Hout * eng.Wout,
                                        1 if eng.need_sigmoid else 0, ptr(ex["target"]), ptr(ex["mask"]), self.mask_c,
                                        ptr(ex["out"]), ptr(ex["partials"]), self.nblk, ptr(ex["loss"]))
+        self._with_out_conv = False        # dip_loss_head_fwd runs the output conv itself
+        self._head_fwd = [(self.lib.dip_loss_head_fwd, (C.byref(self._head),), "loss_head_fwd")]
+        self._head_bwd = [(self.lib.dip_loss_head_bwd, (C.byref(self._head), ex["gl"].data_ptr(), eng.dy_out.data_ptr(),
+                                                        round_up(eng.n_out, 4)), "loss_head_bwd")]
+
+    def _build_row0_sr(self, slab, Cimg, H, W, t0):
+        """Row 0 of a super-resolution group: the buffers of utils.loss_head.SRHead (taps, LR target, HR output, LR output,
+        partials) in the slab, its descriptor and its launches."""
+        from utils import loss_head as LH
+        eng = self.eng
+        geom = LH.sr_geometry(self.downsamplers[0], eng.Hout, eng.Wout, who="GroupedFits")
+        k, f, pad, Ho, Wo = geom
+        if (Ho, Wo) != tuple(t0.shape[2:]):
+            raise ValueError(f"GroupedFits: targets (the LR images) are {tuple(t0.shape[2:])}, the down-sampled net output is "
+                             f"{(Ho, Wo)} (net output {(eng.Hout, eng.Wout)}, k {k}, factor {f}, pad {pad})")
+        self._sr_geom = geom
+        Cn = eng.n_out
+        nin = Cimg * H * W
+        ex = {}
+        ex["saved"] = slab.alloc(nin)
+        ex["noisy"] = slab.alloc(nin) if self.std > 0 else None
+        ex["rng"] = slab.alloc(2, torch.int64, zero=True)
+        ex["taps"] = slab.alloc(k * k)                      # per-instance data: every pointer of a grouped launch is in the slab
+        ex["target"] = slab.alloc(Cn * Ho * Wo)             # img_LR
+        ex["mask"] = None
+        ex["out"] = slab.alloc(Cn * eng.Hout * eng.Wout)    # out_HR, NCHW
+        ex["y"] = slab.alloc(Cn * Ho * Wo)                  # out_LR
+        self.nblk = self.lib.dip_sr_loss_nblk(Cn, Ho, Wo)
+        ex["partials"] = slab.alloc(self.nblk)
+        ex["loss"] = slab.alloc(1, zero=True)
+        ex["gl"] = slab.alloc(1)
+        ex["gl"].fill_(1.0)
+        ex["m"] = slab.alloc(eng.n_arena, zero=True)
+        ex["v"] = slab.alloc(eng.n_arena, zero=True)
+        ex["iter"] = slab.alloc(16, torch.uint8, zero=True)
+        self._row0_extra = ex
+        self._x = ex["noisy"] if self.std > 0 else ex["saved"]
+        self._head = LH.sr_descriptor(eng, geom, ex["out"].data_ptr(), ex["taps"].data_ptr(), ex["target"].data_ptr(),
+                                      ex["y"].data_ptr(), ex["partials"].data_ptr(), self.nblk, ex["loss"].data_ptr())
+        self._with_out_conv = True         # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
+        self._head_fwd = LH.sr_fwd_launches(eng, self._head)
+        self._head_bwd = LH.sr_bwd_launches(eng, self._head, ex["gl"].data_ptr())
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()
@@ -311,11 +402,13 @@ class GroupedFits:
                 N.check(lib.dip_noise_axpy_dev2(ex["saved"].data_ptr(), ex["noisy"].data_ptr(), ex["saved"].numel(), self.std,
                                                 ex["rng"].data_ptr(), st), "noise_axpy_dev2")
             # out = net(net_input); total_loss = mse(out [* mask], target [* mask])
-            eng._launch_forward(self._x.data_ptr(), main, with_out_conv=False)
-            N.check(lib.dip_loss_head_fwd(C.byref(self._head), st), "loss_head_fwd")
+            # (super-resolution: out_LR = downsampler(out); total_loss = mse(out_LR, img_LR))
+            eng._launch_forward(self._x.data_ptr(), main, with_out_conv=self._with_out_conv)
+            for fn, args, name in self._head_fwd:
+                N.check(fn(*args, st), name)
             # total_loss.backward()
-            N.check(lib.dip_loss_head_bwd(C.byref(self._head), ex["gl"].data_ptr(), eng.dy_out.data_ptr(),
-                                          round_up(eng.n_out, 4), st), "loss_head_bwd")
+            for fn, args, name in self._head_bwd:
+                N.check(fn(*args, st), name)
             eng._launch_backward(main)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
             N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")

@@ -117,6 +117,50 @@ class MSEHead:
         return loss, out
 
 
+# ---------------------------------------------------------------- the super-resolution tail, said once
+# SRHead (one fit) and dip_group.GroupedFits(downsamplers=) (B fits through one launch list) check the down-sampler, derive the
+# geometry, fill DipSRLossDesc and list the launches HERE; they differ only in where the buffers live.
+def sr_check_fixed_taps(d, who="SRHead"):
+    """The fused tail applies the FIXED taps: a down-sampler that is (or may be) trained is refused."""
+    if getattr(d, "_dense", False) or getattr(d, "_nondiag", False) or d.downsampler_.weight.requires_grad \
+            or d.downsampler_.bias.requires_grad:
+        raise NotImplementedError(f"dip-amd: {who} covers the fixed-taps Downsampler; a trainable one (opt_over='down', a "
+                                  "loaded non-diagonal weight, or the down-sampler of a skip() net) goes through the "
+                                  "spelled closure: out_LR = downsampler(net(x)); mse(out_LR, img_LR)")
+
+
+def sr_support(d):
+    """(k, factor, pad) of a Downsampler."""
+    return int(d.kernel.shape[0]), int(d.factor), int(d._pad)
+
+
+def sr_geometry(d, H, W, who="SRHead"):
+    """(k, f, pad, Ho, Wo) of down-sampler d behind an H x W network output."""
+    k, f, pad = sr_support(d)
+    if H + 2 * pad < k or W + 2 * pad < k:
+        raise ValueError(f"{who}: the net output {(H, W)} is smaller than the {k}x{k} filter")
+    return k, f, pad, (H + 2 * pad - k) // f + 1, (W + 2 * pad - k) // f + 1
+
+
+def sr_descriptor(eng, geom, out_ptr, taps_ptr, target_ptr, y_ptr, partials_ptr, nblk, loss_ptr):
+    k, f, pad, Ho, Wo = geom
+    return N.DipSRLossDesc(out_ptr, taps_ptr, target_ptr, y_ptr, partials_ptr, nblk, loss_ptr, eng.n_out, eng.Hout, eng.Wout,
+                           k, f, pad, Ho, Wo, 1 if eng.need_sigmoid else 0)
+
+
+def sr_fwd_launches(eng, desc):
+    """dip_head_fwd (NHWC -> NCHW + sigmoid: out_HR as net(x) writes it) + dip_sr_loss_fwd, as (fn, args, name) triples."""
+    Cs = N.round_up(eng.n_out, 4)
+    return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.out, eng.n_out, eng.Hout * eng.Wout, Cs,
+                                    1 if eng.need_sigmoid else 0), "head_fwd"),
+            (eng.lib.dip_sr_loss_fwd, (C.byref(desc),), "sr_loss_fwd")]
+
+
+def sr_bwd_launches(eng, desc, gscale_ptr):
+    return [(eng.lib.dip_sr_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
+             "sr_loss_bwd")]
+
+
 class SRHead:
     """net + fixed-taps Downsampler + MSE (see the module docstring).  `target` (img_LR) may be replaced and the
     down-sampler's state reloaded between calls; `out_LR` is a buffer this object owns and overwrites."""
@@ -149,12 +193,7 @@ class SRHead:
 
     def _check_state(self):
         """The fused tail applies the FIXED taps: a down-sampler that is (or may be) trained is refused at every call."""
-        d = self.downsampler
-        if getattr(d, "_dense", False) or getattr(d, "_nondiag", False) or d.downsampler_.weight.requires_grad \
-                or d.downsampler_.bias.requires_grad:
-            raise NotImplementedError("dip-amd: SRHead covers the fixed-taps Downsampler; a trainable one (opt_over='down', a "
-                                      "loaded non-diagonal weight, or the down-sampler of a skip() net) goes through the "
-                                      "spelled closure: out_LR = downsampler(net(x)); mse(out_LR, img_LR)")
+        sr_check_fixed_taps(self.downsampler)
 
     @property
     def out_LR(self):
@@ -162,12 +201,7 @@ class SRHead:
         return self._y
 
     def _geometry(self, eng):
-        d = self.downsampler
-        k, f, pad = int(d.kernel.shape[0]), int(d.factor), int(d._pad)
-        H, W = eng.Hout, eng.Wout
-        if H + 2 * pad < k or W + 2 * pad < k:
-            raise ValueError(f"SRHead: the net output {(H, W)} is smaller than the {k}x{k} filter")
-        return k, f, pad, (H + 2 * pad - k) // f + 1, (W + 2 * pad - k) // f + 1
+        return sr_geometry(self.downsampler, eng.Hout, eng.Wout)
 
     def _descriptor(self, eng, out, loss):
         """DipSRLossDesc for the engine's current plan (called by SkipEngine.forward and NativeIteration)."""
@@ -187,19 +221,14 @@ class SRHead:
         if self._y is None or tuple(self._y.shape) != (1, Cn, Ho, Wo) or self._y.device != dev:
             self._y = torch.empty((1, Cn, Ho, Wo), dtype=torch.float32, device=dev)
         self._keep = (out.detach(), taps)
-        return N.DipSRLossDesc(out.data_ptr(), taps.data_ptr(), self.target.data_ptr(), self._y.data_ptr(),
-                               self._scratch.data_ptr(), nblk, loss.data_ptr(), Cn, eng.Hout, eng.Wout, k, f, pad, Ho, Wo,
-                               1 if eng.need_sigmoid else 0)
+        return sr_descriptor(eng, (k, f, pad, Ho, Wo), out.data_ptr(), taps.data_ptr(), self.target.data_ptr(), self._y.data_ptr(),
+                             self._scratch.data_ptr(), nblk, loss.data_ptr())
 
     def fwd_launches(self, eng, desc):
-        Cs = N.round_up(eng.n_out, 4)
-        return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.out, eng.n_out, eng.Hout * eng.Wout, Cs,
-                                        1 if eng.need_sigmoid else 0), "head_fwd"),
-                (eng.lib.dip_sr_loss_fwd, (C.byref(desc),), "sr_loss_fwd")]
+        return sr_fwd_launches(eng, desc)
 
     def bwd_launches(self, eng, desc, gscale_ptr):
-        return [(eng.lib.dip_sr_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
-                 "sr_loss_bwd")]
+        return sr_bwd_launches(eng, desc, gscale_ptr)
 
     def _plan_key(self):
         d = self.downsampler

@@ -635,7 +635,9 @@ int dip_loss_head_bwd(const DipLossHeadDesc* d, const float* gscale, float* dy, 
  *             (NHWC, channel stride Cy, pad channels zero, as dip_head_bwd): bit-identical to that chain of three.
  * The descriptor is read when the call launches (`loss` may be rewritten by the host between calls).  Refused with -1 before
  * any launch: a NULL descriptor or field, C, k, f < 1, Ho / Wo != (H + 2 pad - k) / f + 1, nblk != dip_sr_loss_nblk(C, Ho, Wo),
- * Cy < C or Cy % 4 != 0, a grouped launch.  sizeof(DipSRLossDesc) == 96 (LP64). */
+ * Cy < C or Cy % 4 != 0.  Inside dip_group_begin / dip_group_end both calls (and dip_head_fwd in front of them) serve every
+ * instance with ONE dispatch per kernel: all six pointer fields, gscale and dy must lie in instance 0's slab -- the taps too,
+ * so the instances of a group may carry different taps of the same (k, f, pad).  sizeof(DipSRLossDesc) == 96 (LP64). */
 typedef struct DipSRLossDesc {
     const float* out;      /* [C][H*W] NCHW: the network output (input here) */
     const float* taps;     /* [k*k] */
