@@ -22,13 +22,17 @@ namespace {
 // i % show_every != 0, the row is records + 8 * i, and the finalize kernel's last store is counter[0] = i + 1.  i outside
 // [0, capacity) is the overflow guard: nothing is written to records / out_avg / counter and the decision flags are cleared,
 // so the arena_backtrack launch that follows does nothing.
+// GRP (csrc/dip_group.h; DIP_FAM_LOSS): one dispatch for the B monitors of a group.  The monitor's buffers are per-instance
+// data of the slab, so every pointer -- counter, state, partial, records, out_avg, snapshot, params -- is shifted to the
+// workgroup's instance (blockIdx.z) before the same body runs.  A workgroup belongs to exactly one instance: the overflow
+// guard and arena_backtrack's early return stay workgroup-uniform, and each instance takes its own decision.
+// (The partials phase keeps its body in a function of its own: local copies of the pointers in front of the guard's early
+// return reshape the solo kernel's control flow; behind a call it stays, instruction for instruction, what it was.)
 template <bool DEV>
-__global__ __launch_bounds__(256) void fit_monitor_partials_kernel(const float* __restrict__ out,
-                                                                   const float* __restrict__ noisy,
-                                                                   const float* __restrict__ gt, float* __restrict__ avg,
-                                                                   int64_t n, float w, int first,
-                                                                   const int* __restrict__ counter, int capacity,
-                                                                   float* __restrict__ partial) {
+__device__ __forceinline__ void fit_monitor_partials_body(const float* __restrict__ out, const float* __restrict__ noisy,
+                                                          const float* __restrict__ gt, float* __restrict__ avg, int64_t n,
+                                                          float w, int first, const int* __restrict__ counter, int capacity,
+                                                          float* __restrict__ partial) {
     __shared__ float sh[3][256];
     if constexpr (DEV) {
         const int it = counter[0];                // uniform; the finalize launch behind this one advances it
@@ -63,16 +67,37 @@ __global__ __launch_bounds__(256) void fit_monitor_partials_kernel(const float* 
     }
 }
 
+template <bool DEV, bool GRP = false>
+__global__ __launch_bounds__(256) void fit_monitor_partials_kernel(const float* __restrict__ out_,
+                                                                   const float* __restrict__ noisy_,
+                                                                   const float* __restrict__ gt_, float* __restrict__ avg_,
+                                                                   int64_t n, float w, int first,
+                                                                   const int* __restrict__ counter_, int capacity,
+                                                                   float* __restrict__ partial_, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float*, out);
+    DIP_GRP_PTR(const float*, noisy);
+    DIP_GRP_PTR(const float*, gt);
+    DIP_GRP_PTR(float*, avg);
+    DIP_GRP_PTR(const int*, counter);
+    DIP_GRP_PTR(float*, partial);
+    fit_monitor_partials_body<DEV>(out, noisy, gt, avg, n, w, first, counter, capacity, partial);
+}
+
 // record: [loss, mse_noisy, mse_gt, mse_gt_sm, psnr_noisy, psnr_gt, psnr_gt_sm, fell_back]
 // state:  [psnr_noisy_last, restore_flag, have_last, snapshot_flag]
 // DEV = false: `record` is the row and `check` the host's decision; DEV = true: `record` is row 0 of the table and `check`
 // says whether the monitor back-tracks at all.
-template <bool DEV>
-__global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* __restrict__ partial, int nblk, int64_t n,
-                                                                  int have_gt, const float* __restrict__ loss,
-                                                                  float* __restrict__ record, float* __restrict__ state,
-                                                                  int check, float thresh_db, int* __restrict__ counter,
-                                                                  int capacity, int show_every) {
+template <bool DEV, bool GRP = false>
+__global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* __restrict__ partial_, int nblk, int64_t n,
+                                                                  int have_gt, const float* __restrict__ loss_,
+                                                                  float* __restrict__ record_, float* __restrict__ state_,
+                                                                  int check, float thresh_db, int* __restrict__ counter_,
+                                                                  int capacity, int show_every, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float* __restrict__, partial);
+    DIP_GRP_PTR(const float* __restrict__, loss);
+    DIP_GRP_PTR(float* __restrict__, record);
+    DIP_GRP_PTR(float* __restrict__, state);
+    DIP_GRP_PTR(int* __restrict__, counter);
     if (threadIdx.x != 0) return;
     int it = 0;
     if constexpr (DEV) {
@@ -112,8 +137,13 @@ __global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* _
     if constexpr (DEV) counter[0] = it + 1;
 }
 
-__global__ __launch_bounds__(256) void arena_backtrack_kernel(float* __restrict__ params, float* __restrict__ snapshot,
-                                                              int64_t n, const float* __restrict__ state) {
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void arena_backtrack_kernel(float* __restrict__ params_, float* __restrict__ snapshot_,
+                                                              int64_t n, const float* __restrict__ state_,
+                                                              const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(float* __restrict__, params);
+    DIP_GRP_PTR(float* __restrict__, snapshot);
+    DIP_GRP_PTR(const float* __restrict__, state);
     const float restore = state[1], snap = state[3];
     if (restore == 0.f && snap == 0.f) return;
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -144,11 +174,13 @@ extern "C" int dip_fit_monitor(const float* out, const float* noisy, const float
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (n <= 0 || out == nullptr || noisy == nullptr || out_avg == nullptr) DIP_FAIL("fit_monitor: bad arguments");
     const int nblk = dip_fit_monitor_nblk(n);
-    dip_launch(fit_monitor_partials_kernel<false>, dim3(nblk), dim3(256), 0, st, out, noisy, gt, out_avg, n, exp_weight,
-               first, (const int*)nullptr, 0, partial);
+    dip_launch_pair<DIP_FAM_LOSS>(fit_monitor_partials_kernel<false>, fit_monitor_partials_kernel<false, true>, dim3(nblk),
+                                  dim3(256), 0, st, out, noisy, gt, out_avg, n, exp_weight, first, (const int*)nullptr, 0,
+                                  partial);
     DIP_CHECK_LAUNCH();
-    dip_launch(fit_monitor_finalize_kernel<false>, dim3(1), dim3(64), 0, st, (const float*)partial, nblk, n,
-               gt != nullptr ? 1 : 0, loss, record, state, check_backtrack, backtrack_db, (int*)nullptr, 0, 0);
+    dip_launch_pair<DIP_FAM_LOSS>(fit_monitor_finalize_kernel<false>, fit_monitor_finalize_kernel<false, true>, dim3(1),
+                                  dim3(64), 0, st, (const float*)partial, nblk, n, gt != nullptr ? 1 : 0, loss, record, state,
+                                  check_backtrack, backtrack_db, (int*)nullptr, 0, 0);
     DIP_CHECK_LAUNCH();
     return 0;
 }
@@ -161,12 +193,14 @@ extern "C" int dip_fit_monitor_dev(const DipFitMonitorDesc* d, void* stream) {
         DIP_FAIL("fit_monitor_dev: a required pointer is NULL");
     if (d->n <= 0 || d->capacity <= 0 || d->show_every <= 0) DIP_FAIL("fit_monitor_dev: n, capacity and show_every must be > 0");
     const int nblk = dip_fit_monitor_nblk(d->n);
-    dip_launch(fit_monitor_partials_kernel<true>, dim3(nblk), dim3(256), 0, st, d->out, d->noisy, d->gt, d->out_avg, d->n,
-               d->exp_weight, 0, (const int*)d->counter, d->capacity, d->partial);
+    dip_launch_pair<DIP_FAM_LOSS>(fit_monitor_partials_kernel<true>, fit_monitor_partials_kernel<true, true>, dim3(nblk),
+                                  dim3(256), 0, st, d->out, d->noisy, d->gt, d->out_avg, d->n, d->exp_weight, 0,
+                                  (const int*)d->counter, d->capacity, d->partial);
     DIP_CHECK_LAUNCH();
-    dip_launch(fit_monitor_finalize_kernel<true>, dim3(1), dim3(64), 0, st, (const float*)d->partial, nblk, d->n,
-               d->gt != nullptr ? 1 : 0, d->loss, d->records, d->state, d->backtracking != 0 ? 1 : 0, d->backtrack_db,
-               d->counter, d->capacity, d->show_every);
+    dip_launch_pair<DIP_FAM_LOSS>(fit_monitor_finalize_kernel<true>, fit_monitor_finalize_kernel<true, true>, dim3(1),
+                                  dim3(64), 0, st, (const float*)d->partial, nblk, d->n, d->gt != nullptr ? 1 : 0, d->loss,
+                                  d->records, d->state, d->backtracking != 0 ? 1 : 0, d->backtrack_db, d->counter,
+                                  d->capacity, d->show_every);
     DIP_CHECK_LAUNCH();
     return 0;
 }
@@ -176,8 +210,9 @@ extern "C" int dip_arena_backtrack(float* params, float* snapshot, int64_t n, co
     if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(snapshot)) & 15)
         DIP_FAIL("arena_backtrack: arenas must be 16-byte aligned");
     const int64_t quads = (n + 3) / 4;
-    dip_launch(arena_backtrack_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), params, snapshot, n, state);
+    dip_launch_pair<DIP_FAM_LOSS>(arena_backtrack_kernel<false>, arena_backtrack_kernel<true>,
+                                  dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                                  params, snapshot, n, state);
     DIP_CHECK_LAUNCH();
     return 0;
 }

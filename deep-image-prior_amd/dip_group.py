@@ -30,6 +30,20 @@ different taps of one (k, factor, pad); there is no mask.
     g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, reg_noise_std=0.03)
     g.out, g.out_LR                 # [B, C, H, W] HR outputs, [B, C, Ho, Wo] their down-sampled versions
 
+The rest of the denoising / restoration closure (denoising.ipynb:214-248, restoration.ipynb:192-211: the exponential average
+of the output, three PSNRs, the parameter checkpoint and the 5 dB fall-back), per fit and with no Python between the iterations:
+`monitor=utils.fit_monitor.GroupedFitMonitor(imgs_gt, ...)`.  The monitor's state -- gt, out_avg, partial sums, records, state,
+counter, snapshot -- is per-instance data of the slab like the targets; dip_fit_monitor_dev and dip_arena_backtrack are issued
+inside the group bracket after the backward pass and before Adam (where monitor.update(out, loss) stands in the eager closure),
+three dispatches for all B, and every instance takes its own snapshot / fall-back decision.  Instance b is bit-identical to
+the same fit on its own under utils.fit_monitor.FitMonitor (tests/test_group_monitor_gpu.py).  The monitor carries the EMA:
+exp_weight= / ema_init= are not combined with it, and out_avg starts from the first output.
+
+    mon = GroupedFitMonitor(imgs_gt, exp_weight=0.99, show_every=100, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, monitor=mon)
+    g.capture(); g.run(num_iter - 3)            # the monitor's launches are part of the ONE hipGraph
+    mon.history()                               # [B, iters, 8]; mon.last(), mon.out_avg (= g.out_avg), mon.state, mon.snapshot
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -79,16 +93,20 @@ class GroupedFits:
     ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
-                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None):
+                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
         ema_init 'first' = out_avg starts as the first output (denoising.ipynb:214-215), 'zeros' = starts at 0.
         downsamplers: None = the denoising / inpainting closure; B fixed-taps Downsamplers of one (k, factor, pad) = the
-        super-resolution closure, targets = the LR images [1,C,Ho,Wo], no masks."""
+        super-resolution closure, targets = the LR images [1,C,Ho,Wo], no masks.
+        monitor: None, or a utils.fit_monitor.GroupedFitMonitor: EMA, PSNR records and back-tracking per instance, inside
+        the launch list (then exp_weight / ema_init stay at their defaults: the monitor carries the weight and starts from
+        the first output, as FitMonitor does)."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
+        self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
@@ -179,12 +197,22 @@ class GroupedFits:
                     if self.downsamplers is not None:
                         self._inst(ex["taps"], b).copy_(self.downsamplers[b]._taps.detach().to(device).float().reshape(-1))
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
+                    if self.monitor is not None and ex["mon_gt"] is not None:
+                        self._inst(ex["mon_gt"], b).copy_(self.monitor.imgs_gt[b].detach().to(device).float().reshape(-1))
             # --- what the caller reads: strided views over the instances
             HWo = eng.Hout * eng.Wout
             self.losses = self._strided(ex["loss"], (B,), ())
             self.out = self._strided(ex["out"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1))
             self.out_avg = torch.zeros((B, oc.Cout, eng.Hout, eng.Wout), dtype=torch.float32, device=device) \
                 if self.exp_weight is not None else None
+            if self.monitor is not None:
+                cap = self.monitor.capacity
+                self.monitor._adopt(self, self._strided(ex["mon_records"], (B, cap, 8), (8, 1)),
+                                    self._strided(ex["mon_state"], (B, 4), (1,)), self._strided(ex["mon_counter"], (B,), ()),
+                                    self._strided(ex["mon_avg"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1)),
+                                    None if ex["mon_snapshot"] is None
+                                    else self._strided(ex["mon_snapshot"], (B, eng.n_arena), (1,)))
+                self.out_avg = self.monitor.out_avg
             self.out_LR = None
             if self.downsamplers is not None:
                 _, _, _, Ho, Wo = self._sr_geom
@@ -196,6 +224,26 @@ class GroupedFits:
     # ------------------------------------------------------------------ construction helpers
     def _devctx(self):
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
+
+    @staticmethod
+    def _check_monitor(monitor, downsamplers, exp_weight, ema_init, targets):
+        """What can be said about `monitor` before anything is planned or allocated."""
+        if monitor is None:
+            return None
+        from utils.fit_monitor import GroupedFitMonitor
+        if not isinstance(monitor, GroupedFitMonitor):
+            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor or None, got "
+                            f"{type(monitor).__name__} (a solo FitMonitor cannot checkpoint a slab row)")
+        if downsamplers is not None:
+            raise NotImplementedError("dip-amd: GroupedFits(monitor=) with downsamplers= is not implemented (the super-resolution "
+                                      "closure records psnr_LR / psnr_HR on two sizes: another record)")
+        if exp_weight is not None or ema_init != "first":
+            raise ValueError("dip-amd: GroupedFits: exp_weight= / ema_init= are not combined with monitor= (the monitor carries "
+                             "exp_weight and starts out_avg from the first output)")
+        if monitor._adopted:
+            raise RuntimeError("dip-amd: this GroupedFitMonitor already belongs to a GroupedFits (a monitor is adopted once)")
+        monitor._check_targets(targets)
+        return monitor
 
     @staticmethod
     def _check_downsamplers(downsamplers, B, masks):
@@ -243,6 +291,12 @@ class GroupedFits:
             for k, a in enumerate(args):
                 if not hasattr(a, "_obj"):
                     visit(name, f"arg{k}", a)
+        if self.monitor is not None:
+            visit("fit_monitor", "desc", self._mdesc)
+            for fn, args, name in self._mon:
+                for k, a in enumerate(args):
+                    if not hasattr(a, "_obj"):
+                        visit(name, f"arg{k}", a)
         for k, t in self._row0_extra.items():
             if t is not None:
                 visit("extra", k, t.data_ptr())
@@ -304,6 +358,30 @@ class GroupedFits:
         self._head_fwd = [(self.lib.dip_loss_head_fwd, (C.byref(self._head),), "loss_head_fwd")]
         self._head_bwd = [(self.lib.dip_loss_head_bwd, (C.byref(self._head), ex["gl"].data_ptr(), eng.dy_out.data_ptr(),
                                                         round_up(eng.n_out, 4)), "loss_head_bwd")]
+        if self.monitor is not None:
+            self._build_row0_monitor(slab, nout)
+
+    def _build_row0_monitor(self, slab, nout):
+        """The monitor's buffers, behind everything else instance 0 owns: what utils.fit_monitor.FitMonitor allocates for a
+        solo fit, as per-instance data of the slab; ONE descriptor over them (noisy = the target, out = the head's output,
+        loss = the slab's loss scalar: nothing is rewritten per iteration) and the launches of an iteration."""
+        eng, ex, m = self.eng, self._row0_extra, self.monitor
+        ex["mon_gt"] = slab.alloc(nout) if m.imgs_gt is not None else None
+        ex["mon_avg"] = slab.alloc(nout, zero=True)
+        ex["mon_partial"] = slab.alloc(4 * self.lib.dip_fit_monitor_nblk(nout))
+        ex["mon_records"] = slab.alloc(m.capacity * 8, zero=True)
+        ex["mon_state"] = slab.alloc(4, zero=True)
+        ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
+        ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._mdesc = N.DipFitMonitorDesc(ptr(ex["out"]), ptr(ex["target"]), ptr(ex["mon_gt"]), ptr(ex["mon_avg"]), nout,
+                                          m.exp_weight, m.backtrack_db, ptr(ex["loss"]), ptr(ex["mon_partial"]),
+                                          ptr(ex["mon_records"]), m.capacity, m.show_every, 1 if m.backtracking else 0, 0,
+                                          ptr(ex["mon_counter"]), ptr(ex["mon_state"]))
+        self._mon = [(self.lib.dip_fit_monitor_dev, (C.byref(self._mdesc),), "fit_monitor_dev")]
+        if m.backtracking:
+            self._mon.append((self.lib.dip_arena_backtrack, (eng.params.data_ptr(), ptr(ex["mon_snapshot"]), eng.n_arena,
+                                                             ptr(ex["mon_state"])), "arena_backtrack"))
 
     def _build_row0_sr(self, slab, Cimg, H, W, t0):
         """Row 0 of a super-resolution group: the buffers of utils.loss_head.SRHead (taps, LR target, HR output, LR output,
@@ -410,6 +488,11 @@ class GroupedFits:
             for fn, args, name in self._head_bwd:
                 N.check(fn(*args, st), name)
             eng._launch_backward(main)
+            # monitor.update(out, total_loss): EMA, PSNRs, record; a fall-back overwrites the parameters after this
+            # iteration's gradients and before Adam (denoising.ipynb:238-248), per instance
+            if self.monitor is not None:
+                for fn, args, name in self._mon:
+                    N.check(fn(*args, st), name)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
             N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")
             N.check(lib.dip_adam_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(), ex["v"].data_ptr(),
@@ -420,7 +503,7 @@ class GroupedFits:
         # ATen, batched over the instances: BatchNorm's num_batches_tracked and the closure's out_avg
         if len(eng.bns):
             self._nbt_all.add_(1)
-        if self.out_avg is not None:
+        if self.out_avg is not None and self.monitor is None:
             if self.iterations == 0 and self.ema_first and not torch.cuda.is_current_stream_capturing():
                 self.out_avg.copy_(self.out)
             else:
@@ -428,15 +511,20 @@ class GroupedFits:
 
     def step(self, n=1):
         """n eager iterations (launches on the current stream + the engine's auxiliary streams)."""
+        if self.monitor is not None:
+            self.monitor._check_room(n)
         if self._dry:
             raise RuntimeError("dip-amd: a dry (host-memory) GroupedFits cannot launch anything")
         with torch.cuda.device(self.device):
             for _ in range(int(n)):
                 self._iteration()
                 self.iterations += 1
+                if self.monitor is not None:
+                    self.monitor.i += 1
 
     def capture(self, warmup=3):
-        """`warmup` eager iterations, then the grouped iteration as ONE hipGraph (replayed by run())."""
+        """`warmup` eager iterations (at least one), then the grouped iteration as ONE hipGraph (replayed by run()).  With a
+        monitor the warm-up iterations are recorded like any other: they count towards monitor.i and its capacity."""
         dev = self.device
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
@@ -454,9 +542,13 @@ class GroupedFits:
     def run(self, n=1):
         if self.graph is None:
             return self.step(n)
+        if self.monitor is not None:
+            self.monitor._check_room(n)
         for _ in range(int(n)):
             self.graph.replay()
         self.iterations += int(n)
+        if self.monitor is not None:
+            self.monitor.i += int(n)
 
     def step_counts(self):
         """Adam's step count of every instance, as the device holds it."""

@@ -22,11 +22,23 @@ The same bookkeeping inside the autograd-free iteration (no Python between the i
 There the iteration index is read from device memory (`monitor.counter`, dip_fit_monitor_dev); `monitor.i` stays the host's
 count, and the two forms may alternate on one monitor at any iteration boundary.
 
+B fits through one launch list (dip_group.GroupedFits) carry a GroupedFitMonitor: settings only, until the group adopts it and
+carves its state -- per instance: gt, out_avg, partial sums, records, state, counter, snapshot -- from the slab rows.  Then ONE
+dip_fit_monitor_dev / dip_arena_backtrack call inside the group bracket serves all B, and every instance takes its own
+snapshot / fall-back decision:
+
+    mon = GroupedFitMonitor(imgs_gt, exp_weight=0.99, show_every=100, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, monitor=mon)
+    g.capture(); g.run(num_iter - 3)
+    hist = mon.history()                         # [B, iters, 8] numpy, ONE device->host copy
+    mon.last()[b]["psrn_gt_sm"]; mon.out_avg[b]
+
 Record columns: loss, mse_noisy, mse_gt, mse_gt_sm, psrn_noisy, psrn_gt, psrn_gt_sm, fell_back.
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -136,3 +148,62 @@ class FitMonitor:
         """The latest record as a dict (synchronises)."""
         r = self.records[self.i - 1].cpu().numpy()
         return dict(zip(self.COLUMNS, (float(x) for x in r)))
+
+
+class GroupedFitMonitor:
+    """The bookkeeping of FitMonitor for the B fits of a dip_group.GroupedFits: settings only.  It owns no device memory; the
+    group that adopts it (GroupedFits(..., monitor=this)) places the per-instance buffers in its slab rows and exposes them
+    here as [B, ...] views: records [B, capacity, 8], state [B, 4] (writable), counter [B] int32, out_avg [B, C, H, W] and
+    snapshot [B, n_arena] (None without back-tracking).  `i` is the host's count of issued iterations."""
+    COLUMNS = FitMonitor.COLUMNS
+
+    def __init__(self, imgs_gt=None, exp_weight=0.99, show_every=100, backtrack_db=5.0, backtracking=True, capacity=16384):
+        self.imgs_gt = None if imgs_gt is None else list(imgs_gt)
+        if self.imgs_gt is not None and any(t is None for t in self.imgs_gt):
+            raise ValueError("dip-amd: GroupedFitMonitor: imgs_gt holds one image per instance or is None (all or none)")
+        self.exp_weight, self.show_every, self.backtrack_db = float(exp_weight), int(show_every), float(backtrack_db)
+        self.backtracking, self.capacity = bool(backtracking), int(capacity)
+        if self.show_every <= 0 or self.capacity <= 0:
+            raise ValueError("dip-amd: GroupedFitMonitor: show_every and capacity must be > 0")
+        self.i = 0
+        self._group = None         # weak: the group holds the monitor, and a cycle would keep slab and hipGraph alive
+        self._adopted = False
+        self.records = self.state = self.counter = self.out_avg = self.snapshot = None
+
+    def _check_targets(self, targets):
+        """imgs_gt against the group's targets: one [1,C,H,W] image per instance, shaped like the target."""
+        if self.imgs_gt is None:
+            return
+        if len(self.imgs_gt) != len(targets):
+            raise ValueError(f"dip-amd: GroupedFitMonitor has {len(self.imgs_gt)} imgs_gt for {len(targets)} instances")
+        for b, (gt, t) in enumerate(zip(self.imgs_gt, targets)):
+            if tuple(gt.shape) != tuple(t.shape):
+                raise ValueError(f"dip-amd: GroupedFitMonitor: imgs_gt[{b}] is {tuple(gt.shape)}, the target is {tuple(t.shape)}")
+
+    @property
+    def group(self):
+        """The GroupedFits that adopted this monitor (None before adoption, or once that group is gone)."""
+        return None if self._group is None else self._group()
+
+    def _adopt(self, group, records, state, counter, out_avg, snapshot):
+        self._group, self._adopted = weakref.ref(group), True
+        self.records, self.state, self.counter, self.out_avg, self.snapshot = records, state, counter, out_avg, snapshot
+
+    def _check_room(self, n):
+        """Refuses n more iterations when they do not fit: before anything is issued, eager or replayed."""
+        if self.i + int(n) > self.capacity:
+            raise RuntimeError(f"dip-amd: GroupedFitMonitor capacity exceeded ({self.i} recorded + {int(n)} > capacity "
+                               f"{self.capacity}); construct it with capacity >= num_iter")
+
+    def history(self):
+        """All records so far as a [B, i, 8] float32 numpy array (one device->host copy; synchronises)."""
+        if self.records is None:
+            raise RuntimeError("dip-amd: this GroupedFitMonitor has not been given to a GroupedFits yet")
+        return self.records[:, :self.i].contiguous().cpu().numpy()
+
+    def last(self):
+        """The latest record of every instance: a list of B dicts keyed by COLUMNS (synchronises)."""
+        if self.records is None or self.i < 1:
+            raise RuntimeError("dip-amd: GroupedFitMonitor.last(): nothing has been recorded yet")
+        r = self.records[:, self.i - 1].contiguous().cpu().numpy()
+        return [dict(zip(self.COLUMNS, (float(x) for x in row))) for row in r]

@@ -681,7 +681,12 @@ int dip_fit_monitor(const float* out, const float* noisy, const float* gt, float
  * dip_arena_backtrack behind it does nothing (a guard against out-of-bounds writes; callers check the capacity first).
  * The descriptor is read when the call launches: `loss` (this iteration's loss scalar, or NULL) may be rewritten by the
  * host between calls.  gt may be NULL; every other pointer is required; n, capacity, show_every > 0, otherwise -1 before
- * anything is launched.  sizeof(DipFitMonitorDesc) == 104 (LP64). */
+ * anything is launched.  sizeof(DipFitMonitorDesc) == 104 (LP64).
+ * Inside dip_group_begin / dip_group_end the call serves the B monitors of the group: every non-NULL pointer of the
+ * descriptor (out, noisy, gt, out_avg, loss, partial, records, counter, state) must lie in instance 0's slab, and instance
+ * b works on the same fields advanced by b * stride -- its own counter (so the instances may stand at different iterations;
+ * the overflow guard is per instance), its own record row, out_avg, state and decision.  Two dispatches for all B (family
+ * DIP_FAM_LOSS), or 2 B when that family runs as a host loop. */
 typedef struct DipFitMonitorDesc {
     const float* out;       /* [n] the network output of this iteration */
     const float* noisy;     /* [n] */
@@ -701,7 +706,9 @@ typedef struct DipFitMonitorDesc {
 int dip_fit_monitor_dev(const DipFitMonitorDesc* d, void* stream);
 /* applies the decision in `state` to the flat parameter arena: restore -> params = snapshot,
  * snapshot -> snapshot = params, neither -> nothing (the notebook's net_param.data.copy_(...) /
- * last_net = [x.detach().cpu() ...], :242-247) */
+ * last_net = [x.detach().cpu() ...], :242-247).  Inside dip_group_begin / dip_group_end: params, snapshot and state lie
+ * in instance 0's slab and instance b applies ITS state to ITS params / snapshot (advanced by b * stride), so in one
+ * dispatch some instances restore, some snapshot and some do nothing. */
 int dip_arena_backtrack(float* params, float* snapshot, int64_t n, const float* state, void* stream);
 
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
