@@ -44,6 +44,18 @@ exp_weight= / ema_init= are not combined with it, and out_avg starts from the fi
     g.capture(); g.run(num_iter - 3)            # the monitor's launches are part of the ONE hipGraph
     mon.history()                               # [B, iters, 8]; mon.last(), mon.out_avg (= g.out_avg), mon.state, mon.snapshot
 
+A super-resolution group takes `monitor=utils.fit_monitor.GroupedSRFitMonitor(imgs_HR=None, capacity=...)` instead: the
+psnr_LR / psnr_HR record of super-resolution.ipynb:188-191 per fit (utils.fit_monitor.SRFitMonitor has the columns).  Its
+buffers -- the optional HR ground truth, the partial sums, the records, the counter -- are per-instance data of the slab behind
+everything a monitor-less super-resolution group owns; ONE descriptor and ONE dip_sr_monitor_dev call inside the group bracket,
+after the backward pass and before Adam, serve all B (two dispatches), inside the ONE hipGraph of capture().  Instance b's
+records are bit-identical to the solo NativeIteration + SRFitMonitor fit; the fit itself is untouched, and out_avg stays None
+(this closure has no moving average: exp_weight= / ema_init= are refused with it).
+
+    mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, reg_noise_std=0.03, monitor=mon)
+    g.capture(); g.run(num_iter - 3); mon.history()        # [B, iters, 5]: loss, mse_LR, mse_HR, psnr_LR, psnr_HR
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -102,7 +114,8 @@ class GroupedFits:
         super-resolution closure, targets = the LR images [1,C,Ho,Wo], no masks.
         monitor: None, or a utils.fit_monitor.GroupedFitMonitor: EMA, PSNR records and back-tracking per instance, inside
         the launch list (then exp_weight / ema_init stay at their defaults: the monitor carries the weight and starts from
-        the first output, as FitMonitor does)."""
+        the first output, as FitMonitor does); with downsamplers= a utils.fit_monitor.GroupedSRFitMonitor: the psnr_LR /
+        psnr_HR record per instance (no moving average: exp_weight / ema_init stay at their defaults, out_avg stays None)."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
@@ -197,15 +210,20 @@ class GroupedFits:
                     if self.downsamplers is not None:
                         self._inst(ex["taps"], b).copy_(self.downsamplers[b]._taps.detach().to(device).float().reshape(-1))
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
-                    if self.monitor is not None and ex["mon_gt"] is not None:
+                    if ex.get("mon_gt") is not None:
                         self._inst(ex["mon_gt"], b).copy_(self.monitor.imgs_gt[b].detach().to(device).float().reshape(-1))
+                    if ex.get("mon_hr") is not None:
+                        self._inst(ex["mon_hr"], b).copy_(self.monitor.imgs_HR[b].detach().to(device).float().reshape(-1))
             # --- what the caller reads: strided views over the instances
             HWo = eng.Hout * eng.Wout
             self.losses = self._strided(ex["loss"], (B,), ())
             self.out = self._strided(ex["out"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1))
             self.out_avg = torch.zeros((B, oc.Cout, eng.Hout, eng.Wout), dtype=torch.float32, device=device) \
                 if self.exp_weight is not None else None
-            if self.monitor is not None:
+            if self.monitor is not None and self.downsamplers is not None:
+                self.monitor._adopt(self, self._strided(ex["mon_records"], (B, self.monitor.capacity, 5), (5, 1)),
+                                    self._strided(ex["mon_counter"], (B,), ()))
+            elif self.monitor is not None:
                 cap = self.monitor.capacity
                 self.monitor._adopt(self, self._strided(ex["mon_records"], (B, cap, 8), (8, 1)),
                                     self._strided(ex["mon_state"], (B, 4), (1,)), self._strided(ex["mon_counter"], (B,), ()),
@@ -230,19 +248,29 @@ class GroupedFits:
         """What can be said about `monitor` before anything is planned or allocated."""
         if monitor is None:
             return None
-        from utils.fit_monitor import GroupedFitMonitor
-        if not isinstance(monitor, GroupedFitMonitor):
-            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor or None, got "
-                            f"{type(monitor).__name__} (a solo FitMonitor cannot checkpoint a slab row)")
-        if downsamplers is not None:
-            raise NotImplementedError("dip-amd: GroupedFits(monitor=) with downsamplers= is not implemented (the super-resolution "
-                                      "closure records psnr_LR / psnr_HR on two sizes: another record)")
+        from utils.fit_monitor import GroupedFitMonitor, GroupedSRFitMonitor
+        if not isinstance(monitor, (GroupedFitMonitor, GroupedSRFitMonitor)):
+            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor or "
+                            f"None, got {type(monitor).__name__} (a solo FitMonitor cannot checkpoint a slab row)")
+        sr = isinstance(monitor, GroupedSRFitMonitor)
+        if downsamplers is not None and not sr:
+            raise NotImplementedError("dip-amd: GroupedFits(monitor=GroupedFitMonitor) with downsamplers= is not implemented (the "
+                                      "super-resolution closure records psnr_LR / psnr_HR on two sizes: another record, "
+                                      "utils.fit_monitor.GroupedSRFitMonitor)")
+        if sr and downsamplers is None:
+            raise ValueError("dip-amd: a GroupedSRFitMonitor records out_LR and out_HR of a super-resolution group: it needs "
+                             "GroupedFits(downsamplers=...) (the denoising closure's monitor is GroupedFitMonitor)")
         if exp_weight is not None or ema_init != "first":
-            raise ValueError("dip-amd: GroupedFits: exp_weight= / ema_init= are not combined with monitor= (the monitor carries "
-                             "exp_weight and starts out_avg from the first output)")
+            raise ValueError("dip-amd: GroupedFits: exp_weight= / ema_init= are not combined with monitor= (" +
+                             ("the super-resolution closure has no moving average of the output)" if sr else
+                              "the monitor carries exp_weight and starts out_avg from the first output)"))
         if monitor._adopted:
-            raise RuntimeError("dip-amd: this GroupedFitMonitor already belongs to a GroupedFits (a monitor is adopted once)")
-        monitor._check_targets(targets)
+            raise RuntimeError(f"dip-amd: this {type(monitor).__name__} already belongs to a GroupedFits (a monitor is adopted "
+                               "once)")
+        if sr:
+            monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _build_row0_sr_monitor)
+        else:
+            monitor._check_targets(targets)
         return monitor
 
     @staticmethod
@@ -420,6 +448,28 @@ class GroupedFits:
         self._with_out_conv = True         # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
         self._head_fwd = LH.sr_fwd_launches(eng, self._head)
         self._head_bwd = LH.sr_bwd_launches(eng, self._head, ex["gl"].data_ptr())
+        if self.monitor is not None:
+            self._build_row0_sr_monitor(slab)
+
+    def _build_row0_sr_monitor(self, slab):
+        """The super-resolution monitor's buffers, behind everything else instance 0 owns: the optional HR ground truth, the
+        partial sums, the records and the counter of utils.fit_monitor.SRFitMonitor as per-instance data of the slab; ONE
+        descriptor over them (out_HR / out_LR = the head's two outputs, img_LR = the target, loss = the slab's loss scalar:
+        nothing is rewritten per iteration) and the ONE launch of an iteration."""
+        eng, ex, m = self.eng, self._row0_extra, self.monitor
+        _, _, _, Ho, Wo = self._sr_geom
+        Cn = eng.n_out
+        m._check_hr(self.B, (1, Cn, eng.Hout, eng.Wout))
+        n_hr, n_lr = Cn * eng.Hout * eng.Wout, Cn * Ho * Wo
+        ex["mon_hr"] = slab.alloc(n_hr) if m.imgs_HR is not None else None
+        ex["mon_partial"] = slab.alloc(self.lib.dip_fit_monitor_nblk(n_hr) + self.lib.dip_fit_monitor_nblk(n_lr))
+        ex["mon_records"] = slab.alloc(m.capacity * 5, zero=True)
+        ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._mdesc = N.DipSRMonitorDesc(ptr(ex["out"]), ptr(ex["y"]), ptr(ex["mon_hr"]), ptr(ex["target"]), n_hr, n_lr,
+                                         ptr(ex["loss"]), ptr(ex["mon_partial"]), ptr(ex["mon_records"]), m.capacity, 0,
+                                         ptr(ex["mon_counter"]))
+        self._mon = [(self.lib.dip_sr_monitor_dev, (C.byref(self._mdesc),), "sr_monitor_dev")]
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()
@@ -490,6 +540,7 @@ class GroupedFits:
             eng._launch_backward(main)
             # monitor.update(out, total_loss): EMA, PSNRs, record; a fall-back overwrites the parameters after this
             # iteration's gradients and before Adam (denoising.ipynb:238-248), per instance
+            # (super-resolution: monitor.update(out_HR, out_LR, total_loss): the psnr_LR / psnr_HR record)
             if self.monitor is not None:
                 for fn, args, name in self._mon:
                     N.check(fn(*args, st), name)

@@ -119,6 +119,12 @@ class DipFitMonitorDesc(C.Structure):
                 ("reserved", C.c_int32), ("counter", C.c_void_p), ("state", C.c_void_p)]
 
 
+class DipSRMonitorDesc(C.Structure):
+    _fields_ = [("out_HR", C.c_void_p), ("out_LR", C.c_void_p), ("img_HR", C.c_void_p), ("img_LR", C.c_void_p),
+                ("n_hr", C.c_int64), ("n_lr", C.c_int64), ("loss", C.c_void_p), ("partial", C.c_void_p),
+                ("records", C.c_void_p), ("capacity", C.c_int32), ("reserved", C.c_int32), ("counter", C.c_void_p)]
+
+
 _SIGS = {
     "dip_abi_version": (C.c_int, []),
     "dip_build_id": (C.c_char_p, []),
@@ -260,6 +266,9 @@ _SIGS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "dip_fit_monitor_dev": (C.c_int, [C.POINTER(DipFitMonitorDesc), C.c_void_p]),
     "dip_arena_backtrack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "dip_sr_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "dip_sr_monitor_dev": (C.c_int, [C.POINTER(DipSRMonitorDesc), C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),
     "dip_lanczos_down_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -16,7 +16,8 @@ captures ONE launch list that serves all of them (every kernel launch covers all
 `NativeIteration` is the eager form without autograd: head (utils.loss_head.MSEHead or SRHead), reg-noise (utils.reg_noise.RegNoise) and
 optimiser known statically, the whole iteration -- noise, forward list, loss head, backward list, Adam -- is ONE call into
 the library (dip_iter_run), bit-identical to {zero_grad(); closure(); step()} and interchangeable with it at any iteration.
-With monitor=utils.fit_monitor.FitMonitor(...) the same call also does the closure's bookkeeping (EMA, PSNRs, back-tracking).
+With monitor=utils.fit_monitor.FitMonitor(...) the same call also does the closure's bookkeeping (EMA, PSNRs, back-tracking);
+with an SRHead and monitor=utils.fit_monitor.SRFitMonitor(...) the super-resolution closure's (psnr_LR / psnr_HR).
 """
 from __future__ import annotations
 
@@ -339,6 +340,18 @@ class NativeIteration:
     runs WITH the output conv and the head's launches are dip_head_fwd + dip_sr_loss_fwd and dip_sr_loss_bwd; `it.out` is
     out_HR, `head.out_LR` the down-sampled output.
 
+    monitor=SRFitMonitor(img_LR, img_HR) with an SRHead is the bookkeeping of the super-resolution closure
+    (super-resolution.ipynb:188-191: psnr_LR, psnr_HR, psnr_history.append) in the same slot: ONE launch entry,
+    dip_sr_monitor_dev, whose descriptor points at `it.out` (out_HR), the head's out_LR buffer and the monitor's images, with
+    the loss address handled like FitMonitor's.  It reads and advances `monitor.counter` the same way, so eager
+    `monitor.update(out_HR, head.out_LR, loss)` calls and native iterations alternate on one monitor.  It does not touch the
+    fit: parameters and losses are bit-identical to monitor=None.  An SRFitMonitor with an MSEHead, images that do not match
+    the head's LR size / the net output, and a monitor on another device are refused before anything is issued.
+
+        monitor = SRFitMonitor(img_LR, img_HR, capacity=num_iter)
+        it = NativeIteration(net, SRHead(net, img_LR, downsampler), opt, net_input, reg_noise=reg, monitor=monitor)
+        it.run(num_iter); psnr_history = monitor.history()[:, 3:5]
+
     step() / run(n) past the monitor's capacity raise before anything is issued.  The monitor's buffers and settings are
     part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt)."""
 
@@ -387,6 +400,7 @@ class NativeIteration:
             if reg_noise.saved.shape != net_input.shape or reg_noise.saved.device != net_input.device:
                 raise ValueError("dip-amd: the RegNoise was built for another net_input")
         self.head, self.opt = head, optimizer
+        self._check_monitor()                     # (now with the head: an SRFitMonitor records the two outputs of an SRHead)
         self.net_input, self.reg = net_input.detach(), reg_noise
         self.out = None
         self.iterations = 0
@@ -406,15 +420,21 @@ class NativeIteration:
 
     def _check_monitor(self):
         """What can be said about `monitor` before the output size is known (the image shape: _build)."""
-        from utils.fit_monitor import FitMonitor
+        from utils.fit_monitor import FitMonitor, SRFitMonitor
+        from utils.loss_head import SRHead
         m = self.monitor
         if m is None:
             return
-        if not isinstance(m, FitMonitor):
-            raise TypeError(f"dip-amd: monitor must be a utils.fit_monitor.FitMonitor or None, got {type(m).__name__}")
+        if not isinstance(m, (FitMonitor, SRFitMonitor)):
+            raise TypeError("dip-amd: monitor must be a utils.fit_monitor.FitMonitor, an SRFitMonitor or None, got "
+                            f"{type(m).__name__}")
+        head = getattr(self, "head", None)
+        if isinstance(m, SRFitMonitor) and head is not None and not isinstance(head, SRHead):
+            raise TypeError(f"dip-amd: an SRFitMonitor records out_LR and out_HR of a utils.loss_head.SRHead, the head is a "
+                            f"{type(head).__name__} (use a FitMonitor)")
         if m.dev != self.device:
-            raise RuntimeError(f"dip-amd: the FitMonitor lives on {m.dev}, the iteration runs on {self.device}")
-        if m.engine is not None and m.engine is not self.engine:
+            raise RuntimeError(f"dip-amd: the {type(m).__name__} lives on {m.dev}, the iteration runs on {self.device}")
+        if isinstance(m, FitMonitor) and m.engine is not None and m.engine is not self.engine:
             raise ValueError("dip-amd: the FitMonitor back-tracks another net (it was built for a different skip() net)")
 
     # -------------------------------------------------------------------------------------------- the command arrays
@@ -427,9 +447,7 @@ class NativeIteration:
                 opt.lr, opt.betas, opt.eps, id(opt._groups),
                 head._plan_key(),
                 None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
-            + (() if m is None else ((id(m), id(m.records), id(m.state), id(m.out_avg), id(m.partial), id(m.snapshot),
-                                      id(m.counter), m.exp_weight, m.show_every, m.backtrack_db, id(m.noisy), id(m.gt),
-                                      id(m.engine), m.capacity, m.n),))          # (monitor=None: the key as it was)
+            + (() if m is None else (m._plan_key(),))          # (monitor=None: the key as it was)
 
     def _build(self):
         eng, head, opt, reg, m = self.engine, self.head, self.opt, self.reg, self.monitor
@@ -446,10 +464,14 @@ class NativeIteration:
         out = self.out
         if out is None or tuple(out.shape) != (1, eng.n_out, eng.Hout, eng.Wout) or out.device != dev:
             out = torch.empty((1, eng.n_out, eng.Hout, eng.Wout), dtype=torch.float32, device=dev)
-        if m is not None and tuple(m.noisy.shape) != tuple(out.shape):
+        from utils.fit_monitor import SRFitMonitor
+        sr_mon = isinstance(m, SRFitMonitor)
+        if m is not None and not sr_mon and tuple(m.noisy.shape) != tuple(out.shape):
             raise ValueError(f"dip-amd: the FitMonitor's image is {tuple(m.noisy.shape)}, the net output is {tuple(out.shape)}")
         loss0 = torch.zeros((), dtype=torch.float32, device=dev)
         desc = head._descriptor(eng, out, loss0)
+        if sr_mon:                                # (the head's LR buffer exists now: img_LR / img_HR against the two outputs)
+            m._check_outputs(out.shape, head.out_LR.shape, who="NativeIteration")
         pre = []
         if noisy:
             pre.append((lib.dip_noise_axpy_dev, (reg.saved.data_ptr(), reg.out.data_ptr(), reg.saved.numel(), reg.std,
@@ -475,10 +497,11 @@ class NativeIteration:
         if m is not None:
             # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the
             # parameters after this iteration's gradients were computed and before Adam applies them
-            mdesc = m._dev_descriptor(out)
+            mdesc = m._dev_descriptor(out, head.out_LR) if sr_mon else m._dev_descriptor(out)
             mdesc.loss = loss0.data_ptr()
-            mon = [(lib.dip_fit_monitor_dev, (C.byref(mdesc),), "fit_monitor_dev")]
-            if m.engine is not None:
+            mon = [(lib.dip_sr_monitor_dev, (C.byref(mdesc),), "sr_monitor_dev")] if sr_mon else \
+                [(lib.dip_fit_monitor_dev, (C.byref(mdesc),), "fit_monitor_dev")]
+            if not sr_mon and m.engine is not None:
                 snap = m._ensure_snapshot()
                 mon.append((lib.dip_arena_backtrack, (eng.params.data_ptr(), snap.data_ptr(), eng.params.numel(),
                                                       m.state.data_ptr()), "arena_backtrack"))
@@ -491,8 +514,7 @@ class NativeIteration:
                           keep=(head._plan_keep(), eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
                                 None if reg is None else (reg.saved, reg.out, reg.offset),
-                                None if m is None else (m, m.records, m.state, m.out_avg, m.partial, m.snapshot, m.counter,
-                                                        m.noisy, m.gt, m.engine)))
+                                None if m is None else m._plan_keep()))
         self._key = self._signature(opt._sig)
 
     # -------------------------------------------------------------------------------------------- run
@@ -503,7 +525,7 @@ class NativeIteration:
         self.head._check_state()                  # (an SRHead's down-sampler may have become trainable)
         m = self.monitor
         if m is not None and m.i + n > m.capacity:
-            raise RuntimeError(f"dip-amd: FitMonitor capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
+            raise RuntimeError(f"dip-amd: {type(m).__name__} capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
                                "construct it with capacity >= num_iter")
         # (the parameters' addresses are part of the key: they also say that the engine's arena still holds the parameters)
         if self._signature(self.opt._signature()) != self._key:
@@ -519,7 +541,7 @@ class NativeIteration:
     def _issue(self, loss_ptr, ptrs):
         self._plan["desc"].loss = loss_ptr        # read by the head's forward launch (dip_loss_head_fwd / dip_sr_loss_fwd)
         if self._plan["mdesc"] is not None:
-            self._plan["mdesc"].loss = loss_ptr   # column 0 of this iteration's record (read by dip_fit_monitor_dev)
+            self._plan["mdesc"].loss = loss_ptr   # column 0 of this iteration's record (dip_fit_monitor_dev / dip_sr_monitor_dev)
         self._plan["lists"].run(ptrs)
 
     def _finish(self, n):

@@ -34,6 +34,27 @@ snapshot / fall-back decision:
     mon.last()[b]["psrn_gt_sm"]; mon.out_avg[b]
 
 Record columns: loss, mse_noisy, mse_gt, mse_gt_sm, psrn_noisy, psrn_gt, psrn_gt_sm, fell_back.
+
+The super-resolution closure (super-resolution.ipynb:169-191, sr_prior_effect.ipynb cell 6) keeps another record: after
+backward() it computes psnr_LR = compare_psnr(LR_np, out_LR) and psnr_HR = compare_psnr(HR_np, out_HR) on the host -- two
+device-to-host copies and two synchronisations per iteration -- and has no EMA and no back-tracking.  SRFitMonitor is that
+record on the device (dip_sr_monitor: one streaming pass over both sizes, a one-block finalize; columns loss, mse_LR, mse_HR,
+psnr_LR, psnr_HR; img_HR is optional):
+
+    mon = SRFitMonitor(img_LR_var, img_HR_var, capacity=num_iter)
+    def closure():
+        total_loss, out_HR = head(net_input)                 # head = utils.loss_head.SRHead(net, img_LR_var, downsampler)
+        total_loss.backward()
+        mon.update(out_HR, head.out_LR, total_loss)          # no host sync
+        return total_loss
+    psnr_history = mon.history()[:, 3:5]                     # [iters, 5] numpy, ONE device->host copy
+
+    it = NativeIteration(net, head, opt, net_input, reg_noise=reg, monitor=mon)     # the same record inside the one call:
+    it.run(n); mon.last()["psnr_HR"]                                               # dip_sr_monitor_dev, indexed by mon.counter
+
+    mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)                           # B fits: settings only, adopted once
+    g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, monitor=mon)     # ONE dip_sr_monitor_dev call for all B,
+    g.capture(); g.run(num_iter - 3); mon.history()                                 # part of the ONE hipGraph; [B, iters, 5]
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
 """
@@ -46,31 +67,61 @@ import torch
 import dip_native as N
 
 
-class FitMonitor:
+class _DeviceRecords:
+    """What FitMonitor and SRFitMonitor share: a [capacity, len(COLUMNS)] record table in device memory, the host's count `i`
+    of recorded iterations, and the device counter the *_dev kernels index the table with (NativeIteration(monitor=))."""
+    COLUMNS = ()
+
+    def _init_records(self, dev, capacity):
+        self.lib = N.lib()
+        self.dev = dev
+        self.capacity = int(capacity)
+        self.records = torch.zeros((self.capacity, len(self.COLUMNS)), dtype=torch.float32, device=dev)
+        self.i = 0
+        # the iteration index as the *_dev kernels read it (NativeIteration(monitor=)), and the value it will hold once
+        # all issued work has run; update() passes `i` by value and leaves both alone, NativeIteration re-aligns them
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._counter_host = 0
+
+    def _sync_counter(self):
+        """Sets the device counter to `i` on the current stream when it would not hold it (update() calls since the last
+        native iteration, or an `i` set by hand)."""
+        if self._counter_host != self.i:
+            self.counter.fill_(self.i)
+            self._counter_host = self.i
+
+    def _advance(self, n):
+        """n iterations were issued through the device-indexed entry point."""
+        self.i += n
+        self._counter_host += n
+
+    def history(self):
+        """All records so far as a [iters, len(COLUMNS)] float32 numpy array (synchronises once)."""
+        return self.records[:self.i].cpu().numpy()
+
+    def last(self):
+        """The latest record as a dict (synchronises)."""
+        r = self.records[self.i - 1].cpu().numpy()
+        return dict(zip(self.COLUMNS, (float(x) for x in r)))
+
+
+class FitMonitor(_DeviceRecords):
     COLUMNS = ("loss", "mse_noisy", "mse_gt", "mse_gt_sm", "psrn_noisy", "psrn_gt", "psrn_gt_sm", "fell_back")
 
     def __init__(self, net, img_noisy, img_gt=None, exp_weight=0.99, show_every=100, backtrack_db=5.0,
                  backtracking=True, capacity=16384):
         if not img_noisy.is_cuda:
             raise RuntimeError("dip-amd: FitMonitor works on MI355X tensors only (no CPU fallback)")
-        self.lib = N.lib()
-        self.dev = img_noisy.device
+        self._init_records(img_noisy.device, capacity)
         self.noisy = img_noisy.detach().contiguous().float()
         self.gt = None if img_gt is None else img_gt.detach().to(self.dev).contiguous().float()
         if self.gt is not None and self.gt.shape != self.noisy.shape:
             raise ValueError("FitMonitor: img_gt and img_noisy differ in shape")
         self.n = self.noisy.numel()
         self.exp_weight, self.show_every, self.backtrack_db = float(exp_weight), int(show_every), float(backtrack_db)
-        self.capacity = int(capacity)
-        self.records = torch.zeros((self.capacity, 8), dtype=torch.float32, device=self.dev)
         self.state = torch.zeros(4, dtype=torch.float32, device=self.dev)
         self.partial = torch.empty(4 * self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float32, device=self.dev)
         self.out_avg = torch.zeros_like(self.noisy)
-        self.i = 0
-        # the iteration index as dip_fit_monitor_dev reads it (NativeIteration(monitor=)), and the value it will hold once
-        # all issued work has run; update() passes `i` by value and leaves both alone, NativeIteration re-aligns them
-        self.counter = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._counter_host = 0
         self.engine = None
         self.snapshot = None
         if backtracking:
@@ -128,29 +179,142 @@ class FitMonitor:
                                    self.backtrack_db, None, ptr(self.partial), ptr(self.records), self.capacity,
                                    self.show_every, 1 if self.engine is not None else 0, 0, ptr(self.counter), ptr(self.state))
 
-    def _sync_counter(self):
-        """Sets the device counter to `i` on the current stream when it would not hold it (update() calls since the last
-        native iteration, or an `i` set by hand)."""
-        if self._counter_host != self.i:
-            self.counter.fill_(self.i)
-            self._counter_host = self.i
+    def _plan_key(self):
+        """What a compiled command array (dip_optim.NativeIteration) was built from: buffers by identity, settings by value."""
+        return (id(self), id(self.records), id(self.state), id(self.out_avg), id(self.partial), id(self.snapshot),
+                id(self.counter), self.exp_weight, self.show_every, self.backtrack_db, id(self.noisy), id(self.gt),
+                id(self.engine), self.capacity, self.n)
 
-    def _advance(self, n):
-        """n iterations were issued through dip_fit_monitor_dev."""
-        self.i += n
-        self._counter_host += n
+    def _plan_keep(self):
+        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
+        return (self, self.records, self.state, self.out_avg, self.partial, self.snapshot, self.counter, self.noisy, self.gt,
+                self.engine)
+
+
+class SRFitMonitor(_DeviceRecords):
+    """psnr_LR / psnr_HR of the super-resolution closure (super-resolution.ipynb:188-191) on the device: one record per
+    iteration, {loss, mse_LR, mse_HR, psnr_LR, psnr_HR}, from the two outputs of utils.loss_head.SRHead -- out_HR against
+    img_HR (optional: without it mse_HR = psnr_HR = 0) and out_LR against img_LR.  No EMA, no show_every, no back-tracking
+    and no net: the reference closure has none of them.  update() is the eager form (dip_sr_monitor); NativeIteration(
+    monitor=this) issues dip_sr_monitor_dev, which reads the row index from `counter`."""
+    COLUMNS = ("loss", "mse_LR", "mse_HR", "psnr_LR", "psnr_HR")
+
+    def __init__(self, img_LR, img_HR=None, capacity=16384):
+        if not isinstance(img_LR, torch.Tensor) or not img_LR.is_cuda or (img_HR is not None and not img_HR.is_cuda):
+            raise RuntimeError("dip-amd: SRFitMonitor works on MI355X tensors only (no CPU fallback)")
+        if int(capacity) <= 0:
+            raise ValueError("dip-amd: SRFitMonitor: capacity must be > 0")
+        self._init_records(img_LR.device, capacity)
+        self.img_LR = img_LR.detach().contiguous().float()
+        self.img_HR = None if img_HR is None else img_HR.detach().to(self.dev).contiguous().float()
+        self.n_lr = self.img_LR.numel()
+        self.partial = None
+
+    def _ensure_partial(self, n_hr):
+        """The per-block sums: dip_fit_monitor_nblk(n_hr) + dip_fit_monitor_nblk(n_lr) floats (n_hr is the output's size:
+        without img_HR it is only known when the first output arrives)."""
+        n = self.lib.dip_fit_monitor_nblk(n_hr) + self.lib.dip_fit_monitor_nblk(self.n_lr)
+        if self.partial is None or self.partial.numel() != n:
+            self.partial = torch.empty(n, dtype=torch.float32, device=self.dev)
+        return self.partial
+
+    def _check_outputs(self, hr_shape, lr_shape, who="SRFitMonitor.update"):
+        if tuple(lr_shape) != tuple(self.img_LR.shape):
+            raise ValueError(f"dip-amd: {who}: the SRFitMonitor's img_LR is {tuple(self.img_LR.shape)}, out_LR is "
+                             f"{tuple(lr_shape)}")
+        if self.img_HR is not None and tuple(hr_shape) != tuple(self.img_HR.shape):
+            raise ValueError(f"dip-amd: {who}: the SRFitMonitor's img_HR is {tuple(self.img_HR.shape)}, out_HR is "
+                             f"{tuple(hr_shape)}")
+
+    def update(self, out_HR, out_LR, loss=None):
+        """Call once per closure evaluation, after backward(): mon.update(out_HR, head.out_LR, total_loss)."""
+        if self.i >= self.capacity:
+            raise RuntimeError(f"dip-amd: SRFitMonitor capacity exceeded ({self.i} recorded, capacity {self.capacity}); "
+                               "construct it with capacity >= num_iter")
+        hr, lr = out_HR.detach(), out_LR.detach()
+        if not hr.is_cuda or not lr.is_cuda or hr.device != self.dev or lr.device != self.dev:
+            raise RuntimeError(f"dip-amd: SRFitMonitor.update: the outputs are on {hr.device} / {lr.device}, the monitor "
+                               f"lives on {self.dev} (no CPU fallback)")
+        self._check_outputs(hr.shape, lr.shape)
+        hr, lr = hr.contiguous().float(), lr.contiguous().float()
+        with torch.cuda.device(self.dev):        # raw HIP launches go to the current device's streams
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            lptr = None
+            if loss is not None:
+                self._loss = loss.detach().reshape(1).float()          # keep alive until the launch has run
+                lptr = self._loss.data_ptr()
+            N.check(self.lib.dip_sr_monitor(hr.data_ptr(), lr.data_ptr(),
+                                            self.img_HR.data_ptr() if self.img_HR is not None else None,
+                                            self.img_LR.data_ptr(), hr.numel(), self.n_lr, lptr,
+                                            self._ensure_partial(hr.numel()).data_ptr(), self.records[self.i].data_ptr(),
+                                            stream), "sr_monitor")
+        self._keep = (hr, lr)
+        self.i += 1
+
+    def _dev_descriptor(self, out_HR, out_LR):
+        """DipSRMonitorDesc over this monitor's buffers for the output buffers; `loss` is filled in per iteration."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return N.DipSRMonitorDesc(ptr(out_HR), ptr(out_LR), ptr(self.img_HR), ptr(self.img_LR), out_HR.numel(), self.n_lr,
+                                  None, ptr(self._ensure_partial(out_HR.numel())), ptr(self.records), self.capacity, 0,
+                                  ptr(self.counter))
+
+    def _plan_key(self):
+        return (id(self), id(self.records), id(self.partial), id(self.counter), id(self.img_LR), id(self.img_HR), self.capacity)
+
+    def _plan_keep(self):
+        return (self, self.records, self.partial, self.counter, self.img_LR, self.img_HR)
+
+
+class _GroupedRecords:
+    """What GroupedFitMonitor and GroupedSRFitMonitor share: settings only, until a dip_group.GroupedFits adopts the monitor
+    (once) and exposes the per-instance buffers of its slab rows here as [B, ...] views; `i` is the host's count of issued
+    iterations."""
+    COLUMNS = ()
+
+    def _init_group(self, capacity):
+        self.capacity = int(capacity)
+        self.i = 0
+        self._group = None         # weak: the group holds the monitor, and a cycle would keep slab and hipGraph alive
+        self._adopted = False
+        self.records = self.counter = None
+
+    def _check_images(self, imgs, shapes, name, what):
+        """`imgs` (None, or one [1,C,H,W] image per instance) against the shapes the group works on."""
+        if imgs is None:
+            return
+        who = type(self).__name__
+        if len(imgs) != len(shapes):
+            raise ValueError(f"dip-amd: {who} has {len(imgs)} {name} for {len(shapes)} instances")
+        for b, (im, shape) in enumerate(zip(imgs, shapes)):
+            if tuple(im.shape) != tuple(shape):
+                raise ValueError(f"dip-amd: {who}: {name}[{b}] is {tuple(im.shape)}, {what} is {tuple(shape)}")
+
+    @property
+    def group(self):
+        """The GroupedFits that adopted this monitor (None before adoption, or once that group is gone)."""
+        return None if self._group is None else self._group()
+
+    def _check_room(self, n):
+        """Refuses n more iterations when they do not fit: before anything is issued, eager or replayed."""
+        if self.i + int(n) > self.capacity:
+            raise RuntimeError(f"dip-amd: {type(self).__name__} capacity exceeded ({self.i} recorded + {int(n)} > capacity "
+                               f"{self.capacity}); construct it with capacity >= num_iter")
 
     def history(self):
-        """All records so far as a [iters, 8] float32 numpy array (synchronises once)."""
-        return self.records[:self.i].cpu().numpy()
+        """All records so far as a [B, i, len(COLUMNS)] float32 numpy array (one device->host copy; synchronises)."""
+        if self.records is None:
+            raise RuntimeError(f"dip-amd: this {type(self).__name__} has not been given to a GroupedFits yet")
+        return self.records[:, :self.i].contiguous().cpu().numpy()
 
     def last(self):
-        """The latest record as a dict (synchronises)."""
-        r = self.records[self.i - 1].cpu().numpy()
-        return dict(zip(self.COLUMNS, (float(x) for x in r)))
+        """The latest record of every instance: a list of B dicts keyed by COLUMNS (synchronises)."""
+        if self.records is None or self.i < 1:
+            raise RuntimeError(f"dip-amd: {type(self).__name__}.last(): nothing has been recorded yet")
+        r = self.records[:, self.i - 1].contiguous().cpu().numpy()
+        return [dict(zip(self.COLUMNS, (float(x) for x in row))) for row in r]
 
 
-class GroupedFitMonitor:
+class GroupedFitMonitor(_GroupedRecords):
     """The bookkeeping of FitMonitor for the B fits of a dip_group.GroupedFits: settings only.  It owns no device memory; the
     group that adopts it (GroupedFits(..., monitor=this)) places the per-instance buffers in its slab rows and exposes them
     here as [B, ...] views: records [B, capacity, 8], state [B, 4] (writable), counter [B] int32, out_avg [B, C, H, W] and
@@ -162,48 +326,45 @@ class GroupedFitMonitor:
         if self.imgs_gt is not None and any(t is None for t in self.imgs_gt):
             raise ValueError("dip-amd: GroupedFitMonitor: imgs_gt holds one image per instance or is None (all or none)")
         self.exp_weight, self.show_every, self.backtrack_db = float(exp_weight), int(show_every), float(backtrack_db)
-        self.backtracking, self.capacity = bool(backtracking), int(capacity)
+        self.backtracking = bool(backtracking)
+        self._init_group(capacity)
         if self.show_every <= 0 or self.capacity <= 0:
             raise ValueError("dip-amd: GroupedFitMonitor: show_every and capacity must be > 0")
-        self.i = 0
-        self._group = None         # weak: the group holds the monitor, and a cycle would keep slab and hipGraph alive
-        self._adopted = False
-        self.records = self.state = self.counter = self.out_avg = self.snapshot = None
+        self.state = self.out_avg = self.snapshot = None
 
     def _check_targets(self, targets):
         """imgs_gt against the group's targets: one [1,C,H,W] image per instance, shaped like the target."""
-        if self.imgs_gt is None:
-            return
-        if len(self.imgs_gt) != len(targets):
-            raise ValueError(f"dip-amd: GroupedFitMonitor has {len(self.imgs_gt)} imgs_gt for {len(targets)} instances")
-        for b, (gt, t) in enumerate(zip(self.imgs_gt, targets)):
-            if tuple(gt.shape) != tuple(t.shape):
-                raise ValueError(f"dip-amd: GroupedFitMonitor: imgs_gt[{b}] is {tuple(gt.shape)}, the target is {tuple(t.shape)}")
-
-    @property
-    def group(self):
-        """The GroupedFits that adopted this monitor (None before adoption, or once that group is gone)."""
-        return None if self._group is None else self._group()
+        self._check_images(self.imgs_gt, [t.shape for t in targets], "imgs_gt", "the target")
 
     def _adopt(self, group, records, state, counter, out_avg, snapshot):
         self._group, self._adopted = weakref.ref(group), True
         self.records, self.state, self.counter, self.out_avg, self.snapshot = records, state, counter, out_avg, snapshot
 
-    def _check_room(self, n):
-        """Refuses n more iterations when they do not fit: before anything is issued, eager or replayed."""
-        if self.i + int(n) > self.capacity:
-            raise RuntimeError(f"dip-amd: GroupedFitMonitor capacity exceeded ({self.i} recorded + {int(n)} > capacity "
-                               f"{self.capacity}); construct it with capacity >= num_iter")
 
-    def history(self):
-        """All records so far as a [B, i, 8] float32 numpy array (one device->host copy; synchronises)."""
-        if self.records is None:
-            raise RuntimeError("dip-amd: this GroupedFitMonitor has not been given to a GroupedFits yet")
-        return self.records[:, :self.i].contiguous().cpu().numpy()
+class GroupedSRFitMonitor(_GroupedRecords):
+    """SRFitMonitor for the B fits of a dip_group.GroupedFits(downsamplers=...): settings only.  The group that adopts it
+    places the per-instance buffers -- the optional HR ground truth, the partial sums, the records, the counter -- in its slab
+    rows, behind everything a monitor-less super-resolution group owns, and exposes records [B, capacity, 5] and counter [B]
+    int32 here.  ONE dip_sr_monitor_dev call inside the group bracket serves all B."""
+    COLUMNS = SRFitMonitor.COLUMNS
 
-    def last(self):
-        """The latest record of every instance: a list of B dicts keyed by COLUMNS (synchronises)."""
-        if self.records is None or self.i < 1:
-            raise RuntimeError("dip-amd: GroupedFitMonitor.last(): nothing has been recorded yet")
-        r = self.records[:, self.i - 1].contiguous().cpu().numpy()
-        return [dict(zip(self.COLUMNS, (float(x) for x in row))) for row in r]
+    def __init__(self, imgs_HR=None, capacity=16384):
+        self.imgs_HR = None if imgs_HR is None else list(imgs_HR)
+        if self.imgs_HR is not None and any(t is None for t in self.imgs_HR):
+            raise ValueError("dip-amd: GroupedSRFitMonitor: imgs_HR holds one image per instance or is None (all or none)")
+        self._init_group(capacity)
+        if self.capacity <= 0:
+            raise ValueError("dip-amd: GroupedSRFitMonitor: capacity must be > 0")
+
+    def _check_count(self, B):
+        """What can be said about imgs_HR before the net output's size is known (the shapes: _check_hr)."""
+        if self.imgs_HR is not None and len(self.imgs_HR) != B:
+            raise ValueError(f"dip-amd: GroupedSRFitMonitor has {len(self.imgs_HR)} imgs_HR for {B} instances")
+
+    def _check_hr(self, B, hr_shape):
+        """imgs_HR against the planned net output: one [1,C,H,W] image per instance."""
+        self._check_images(self.imgs_HR, [hr_shape] * B, "imgs_HR", "the net output")
+
+    def _adopt(self, group, records, counter):
+        self._group, self._adopted = weakref.ref(group), True
+        self.records, self.counter = records, counter

@@ -711,6 +711,45 @@ int dip_fit_monitor_dev(const DipFitMonitorDesc* d, void* stream);
  * dispatch some instances restore, some snapshot and some do nothing. */
 int dip_arena_backtrack(float* params, float* snapshot, int64_t n, const float* state, void* stream);
 
+/* The bookkeeping of the super-resolution closure (super-resolution.ipynb:169-191, sr_prior_effect.ipynb cell 6) without
+ * host round trips: after backward() the notebook does, in every iteration,
+ *   psnr_LR = compare_psnr(imgs['LR_np'], torch_to_np(out_LR));  psnr_HR = compare_psnr(imgs['HR_np'], torch_to_np(out_HR))
+ *   psnr_history.append([psnr_LR, psnr_HR])
+ * -- two device-to-host copies and two synchronisations.  Here one streaming pass leaves per-block fp32 partial sums of
+ * (out_HR - img_HR)^2 (n_hr elements) and (out_LR - img_LR)^2 (n_lr elements) -- one grid, the HR blocks in front of the LR
+ * blocks; per thread an fmaf chain over a grid-stride walk, per block a 256-wide LDS tree in a fixed pairing order -- and a
+ * one-block kernel sums them in double, in block order, and writes the row
+ *   record <- {loss, mse_LR, mse_HR, psnr_LR, psnr_HR}       (psnr = -10 log10(mse), data range 1; 5 floats per row)
+ * Deterministic, no float atomics.  img_HR may be NULL (no ground truth: the HR blocks are not launched, mse_HR = psnr_HR = 0);
+ * `loss` is a device scalar or NULL (0).  `partial` is scratch of dip_fit_monitor_nblk(n_hr) + dip_fit_monitor_nblk(n_lr)
+ * floats.  There is no EMA and no back-tracking: the reference closure has neither.
+ * dip_sr_monitor: `record` is the row, by value from the host (the eager closure's update()).
+ * dip_sr_monitor_dev: the iteration index i = counter[0] lives in DEVICE memory, so the arguments do not change between
+ * iterations and the call can be a command of dip_iter_run's lists; the row is records + 5*i and the last store is
+ * counter[0] <- i + 1.  i outside [0, capacity): nothing is written (the guard of dip_fit_monitor_dev; callers check the
+ * capacity first).  The descriptor is read when the call launches: `loss` may be rewritten by the host between calls.
+ * img_HR and loss may be NULL; every other pointer is required; n_hr, n_lr, capacity > 0, otherwise -1 before anything is
+ * launched.  sizeof(DipSRMonitorDesc) == 88 (LP64).
+ * Inside dip_group_begin / dip_group_end both calls serve the B monitors of the group with two dispatches (family
+ * DIP_FAM_LOSS; a workgroup belongs to one instance): every non-NULL pointer must lie in instance 0's slab, and instance b
+ * works on the same fields advanced by b * stride -- its own counter, partial sums and record row. */
+typedef struct DipSRMonitorDesc {
+    const float* out_HR;    /* [n_hr] the network output of this iteration */
+    const float* out_LR;    /* [n_lr] its down-sampled version (DipSRLossDesc.y) */
+    const float* img_HR;    /* [n_hr] or NULL */
+    const float* img_LR;    /* [n_lr] */
+    int64_t n_hr, n_lr;
+    const float* loss;      /* 1 float or NULL: column 0 of the record */
+    float* partial;         /* dip_fit_monitor_nblk(n_hr) + dip_fit_monitor_nblk(n_lr) floats of scratch */
+    float* records;         /* [capacity][5] */
+    int capacity;
+    int reserved;
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+} DipSRMonitorDesc;
+int dip_sr_monitor(const float* out_HR, const float* out_LR, const float* img_HR, const float* img_LR, int64_t n_hr,
+                   int64_t n_lr, const float* loss, float* partial, float* record, void* stream);
+int dip_sr_monitor_dev(const DipSRMonitorDesc* d, void* stream);
+
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
  * k x k stride-`factor` correlation with the fixed taps; NCHW [C][H][W] -> [C][H/f][W/f]. */
