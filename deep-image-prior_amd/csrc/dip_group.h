@@ -82,6 +82,9 @@ template <class F> __host__ __device__ inline void dip_ptrs(DipLossHeadDesc& d, 
 template <class F> __host__ __device__ inline void dip_ptrs(DipSRLossDesc& d, F& f) {
     f(d.out); f(d.taps); f(d.target); f(d.y); f(d.partials); f(d.loss);
 }
+template <class F> __host__ __device__ inline void dip_ptrs(DipSRTVDesc& d, F& f) {
+    dip_ptrs(d.sr, f); f(d.tv_weight); f(d.tv_partials);
+}
 
 struct DipShiftF {
     long long off;

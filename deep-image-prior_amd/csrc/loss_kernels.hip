@@ -423,6 +423,96 @@ __global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d_
     if (tid == 0) d.partials[b] = red[0];
 }
 
+// ---- the TV term of the closure (total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR); utils/sr_utils.py:54-59)
+constexpr int TV_P = SR_T + 1;                 // a 16 x 16 tile of pixels reads the terms of 17 x 17
+constexpr int TV_BW = 64, TV_BH = 16;          // tile of the forward pass: one wave per 64 columns x 4 rows
+enum : int { TV_POW = 0, TV_SQRT = 1, TV_ONE = 2, TV_TWO = 3 };      // exact forms of s^beta, as ATen's pow has them
+
+template <bool TV> using SrBwdDesc = std::conditional_t<TV, DipSRTVDesc, DipSRLossDesc>;
+__device__ __forceinline__ const DipSRLossDesc& sr_part(const DipSRLossDesc& d) { return d; }
+__device__ __forceinline__ const DipSRLossDesc& sr_part(const DipSRTVDesc& d) { return d.sr; }
+
+// s of the term at a pixel: dhd = right - own, dwd = below - own, s = dhd^2 + dwd^2 (one fma; no epsilon: the reference has none)
+__device__ __forceinline__ float tv_s(float dhd, float dwd) { return fmaf(dhd, dhd, __fmul_rn(dwd, dwd)); }
+__device__ __forceinline__ float tv_pow(float s, float beta, int mode) {
+    return mode == TV_SQRT ? sqrtf(s) : mode == TV_ONE ? s : mode == TV_TWO ? __fmul_rn(s, s) : powf(s, beta);
+}
+// g(s) = beta s^(beta - 1); beta < 1 at s == 0 is +inf, and a = inf * 0 = NaN, as autograd over the spelled closure yields
+__device__ __forceinline__ float tv_dpow(float s, float beta, int mode) {
+    return mode == TV_SQRT ? 0.5f / sqrtf(s) : mode == TV_ONE ? 1.f : mode == TV_TWO ? __fmul_rn(2.f, s)
+                                                                                  : __fmul_rn(beta, powf(s, beta - 1.f));
+}
+// a = g(s) dhd, b = g(s) dwd of the term at (y, x) of one channel; zero where the term does not exist (outside the image, the
+// last row, the last column): nothing outside the image is read
+__device__ __forceinline__ void tv_ab(const float* __restrict__ oc, int y, int x, int H, int W, float beta, int mode, float& a,
+                                      float& b) {
+    a = 0.f;
+    b = 0.f;
+    if (y < 0 || x < 0 || y >= H - 1 || x >= W - 1) return;
+    const float o = oc[y * W + x];
+    const float dhd = oc[y * W + x + 1] - o, dwd = oc[(y + 1) * W + x] - o;
+    const float g = tv_dpow(tv_s(dhd, dwd), beta, mode);
+    a = __fmul_rn(g, dhd);
+    b = __fmul_rn(g, dwd);
+}
+
+// Forward of the TV term: a pure stream over out.  A block is one channel's 16 rows x 64 columns; a wave walks 4 rows of its 64
+// columns keeping the row below in registers (the row it loads for `dwd` is the next step's own row), so an element comes from
+// HBM once (the right neighbour is the same cache line; the row under a wave's strip is read twice, by neighbouring waves of
+// one block).  Per lane a chain of adds in row order, then the 256-wide LDS tree -> one partial per block.
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void sr_tv_fwd_kernel(const DipSRTVDesc d_, const int mode, const DipGrpArg<GRP> grp) {
+    DIP_GRP_DESC(DipSRTVDesc, d);
+    __shared__ float red[256];
+    const int H = d.sr.H, W = d.sr.W;
+    const int tid = threadIdx.x;
+    const int ntx = (W + TV_BW - 1) / TV_BW, nty = (H + TV_BH - 1) / TV_BH;
+    const int b = blockIdx.x;
+    const int x = (b % ntx) * TV_BW + (tid & 63), y0 = ((b / ntx) % nty) * TV_BH + (tid >> 6) * 4, c = b / (ntx * nty);
+    const float* oc = d.sr.out + (size_t)c * H * W;
+    const float beta = d.beta;
+    float lsum = 0.f;
+    if (x < W - 1 && y0 < H - 1) {
+        float cur = oc[y0 * W + x], right = oc[y0 * W + x + 1];
+        for (int r = 0; r < 4 && y0 + r < H - 1; ++r) {
+            const float dn = oc[(y0 + r + 1) * W + x], dnr = oc[(y0 + r + 1) * W + x + 1];
+            lsum = __fadd_rn(lsum, tv_pow(tv_s(right - cur, dn - cur), beta, mode));
+            cur = dn;
+            right = dnr;
+        }
+    }
+    red[tid] = lsum;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) d.tv_partials[b] = red[0];
+}
+
+// *loss = (float)(sum_mse / (C Ho Wo) + (double)*tv_weight * sum_tv): both partial ranges in fixed order in fp64, one launch
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void sr_tv_reduce_kernel(const DipSRTVDesc d_, const DipGrpArg<GRP> grp) {
+    DIP_GRP_DESC(DipSRTVDesc, d);
+    __shared__ double dred[2][256];
+    const int tid = threadIdx.x;
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = tid; i < d.sr.nblk; i += 256) s0 += (double)d.sr.partials[i];
+    for (int i = tid; i < d.tv_nblk; i += 256) s1 += (double)d.tv_partials[i];
+    dred[0][tid] = s0;
+    dred[1][tid] = s1;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) {
+            dred[0][tid] += dred[0][tid + st];
+            dred[1][tid] += dred[1][tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid == 0)
+        *d.sr.loss = (float)(dred[0][0] / ((double)d.sr.C * (double)d.sr.Ho * (double)d.sr.Wo) + (double)*d.tv_weight * dred[1][0]);
+}
+
 // Backward: one lane per HR pixel, every channel (four per float4 store); a block is a 16 x 16 tile of HR pixels.  g is
 // lanczos_bwd_kernel's gather over v = ((y - target) * kk) * gs (at most ceil(k / f)^2 terms off the frame; a frame pixel also
 // takes the padded rows / columns that clamp onto it), then head_bwd_kernel's sigmoid factor and NHWC store with zero pad
@@ -430,10 +520,20 @@ __global__ __launch_bounds__(256) void sr_loss_fwd_kernel(const DipSRLossDesc d_
 // channel -- and the taps are formed ONCE per block into LDS (the lanes of a tile read each of them ~ (16 / f + k / f)^2 / 4 times, and
 // y, target would be two loads each time); STAGE = false (a filter whose footprint exceeds the LDS budget) forms v where it
 // is read.
-template <bool STAGE, int K, int F, bool GRP = false>
-__global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d_, const float* __restrict__ gscale_,
-                                                          float* __restrict__ dy_, const int Cy, const DipGrpArg<GRP> grp) {
-    DIP_GRP_DESC(DipSRLossDesc, d);
+//
+// TV (dip_sr_tv_loss_bwd): the same kernel over a DipSRTVDesc adds the gradient of tv_weight * tv_loss(out) (utils/sr_utils.py:54-59
+// through autograd) to g before the sigmoid factor.  With a = g(s) dhd, b = g(s) dwd of the term at a pixel (tv_ab; zero where the
+// term does not exist) pixel p takes -(a + b) of its own term, a of the term to its left and b of the term above it:
+//   t = ((-(a[p] + b[p])) + a[left]) + b[above];   coef = (2.f * tvw) * gs;   g = acc + coef * t      (every op rounded on its own)
+// STAGE forms a and b of the tile and its one-pixel halo to the left and above (TV_P x TV_P per channel) ONCE per block in LDS,
+// so every s and every sqrt / pow is formed once and not three times per pixel; STAGE = false forms them where they are read, by
+// the same function: the same bits.
+template <bool STAGE, int K, int F, bool TV = false, bool GRP = false>
+__global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const SrBwdDesc<TV> dd_, const float* __restrict__ gscale_,
+                                                          float* __restrict__ dy_, const int Cy, const int tv_mode,
+                                                          const DipGrpArg<GRP> grp) {
+    DIP_GRP_DESC(SrBwdDesc<TV>, dd);
+    const DipSRLossDesc& d = sr_part(dd);
     DIP_GRP_PTR(const float*, gscale);
     DIP_GRP_PTR(float*, dy);
     extern __shared__ float sr_lds[];
@@ -442,8 +542,22 @@ __global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d_
     const int tx0 = blockIdx.x * SR_T, ty0 = blockIdx.y * SR_T;
     const int sx = tx0 + (tid & 15), sy = ty0 + (tid >> 4);
     const int k = K ? K : d.k, f = F ? F : d.f, pad = d.pad, Ho = d.Ho, Wo = d.Wo;
-    float* const sr_tap = sr_lds;                  // [k * k]: a lane's taps depend on its pixel's phase, so not scalar loads
-    float* const sr_v = sr_lds + k * k;
+    const int ntv = (TV && STAGE) ? d.C * TV_P * TV_P : 0;
+    float* const tv_a = sr_lds;                    // [C][TV_P][TV_P], origin (ty0 - 1, tx0 - 1); tv_b behind it
+    float* const tv_b = sr_lds + ntv;
+    float* const sr_tap = sr_lds + 2 * ntv;        // [k * k]: a lane's taps depend on its pixel's phase, so not scalar loads
+    float* const sr_v = sr_tap + k * k;
+    float tv_beta = 0.f, tv_coef = 0.f;
+    if constexpr (TV) {
+        tv_beta = dd.beta;
+        tv_coef = __fmul_rn(__fmul_rn(2.f, *dd.tv_weight), gscale != nullptr ? *gscale : 1.f);
+        if constexpr (STAGE) {
+            for (int idx = tid; idx < ntv; idx += 256) {
+                const int c = idx / (TV_P * TV_P), li = idx - c * (TV_P * TV_P), r = li / TV_P, q = li - r * TV_P;
+                tv_ab(d.out + (size_t)c * HW, ty0 - 1 + r, tx0 - 1 + q, d.H, d.W, tv_beta, tv_mode, tv_a[idx], tv_b[idx]);
+            }
+        }
+    }
     const size_t HWo = (size_t)Ho * Wo;
     const float gs = gscale != nullptr ? *gscale : 1.f;
     const float kk = 2.f / ((float)d.C * (float)(Ho * Wo));
@@ -515,6 +629,23 @@ __global__ __launch_bounds__(256) void sr_loss_bwd_kernel(const DipSRLossDesc d_
             float g = 0.f;
             if (e < nc) {
                 g = acc[e];
+                if constexpr (TV) {
+                    float a, b, al, bu, unused;
+                    if constexpr (STAGE) {
+                        const int li = (c0 + e) * (TV_P * TV_P) + (sy - ty0 + 1) * TV_P + (sx - tx0 + 1);
+                        a = tv_a[li];
+                        b = tv_b[li];
+                        al = tv_a[li - 1];
+                        bu = tv_b[li - TV_P];
+                    } else {
+                        const float* oc = d.out + (size_t)(c0 + e) * HW;
+                        tv_ab(oc, sy, sx, d.H, d.W, tv_beta, tv_mode, a, b);
+                        tv_ab(oc, sy, sx - 1, d.H, d.W, tv_beta, tv_mode, al, unused);
+                        tv_ab(oc, sy - 1, sx, d.H, d.W, tv_beta, tv_mode, unused, bu);
+                    }
+                    const float t = __fadd_rn(__fadd_rn(-__fadd_rn(a, b), al), bu);
+                    g = __fadd_rn(g, __fmul_rn(tv_coef, t));
+                }
                 if (d.sigmoid) {
                     const float o = d.out[(size_t)(c0 + e) * HW + p];
                     g = g * ((1.f - o) * o);     // aten sigmoid_backward: grad * (1 - y) * y
@@ -549,9 +680,8 @@ extern "C" int dip_sr_loss_nblk(int C, int Ho, int Wo) {
     return C * dip_cdiv(Ho, SR_T) * dip_cdiv(Wo, SR_T);
 }
 
-extern "C" int dip_sr_loss_fwd(const DipSRLossDesc* dp, void* stream) {
-    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
-    const DipSRLossDesc& d = *dp;
+// the down-sampler + MSE partials of both forwards: the same instantiations, so y is the same bits with and without TV
+static int sr_fwd_launch(const DipSRLossDesc& d, hipStream_t st) {
     // the phase-split window: qn columns per phase; pitch >= f qn with f * pitch = 16 (mod 32) where one exists (see the kernel)
     const int wc = (SR_T - 1) * d.f + d.k;
     const int qn = dip_cdiv(wc, d.f);
@@ -562,42 +692,97 @@ extern "C" int dip_sr_loss_fwd(const DipSRLossDesc* dp, void* stream) {
     while (rp > 1 && (size_t)((rp - 1) * d.f + d.k) * pitch * 4 > (size_t)SR_LDS_BYTES) rp >>= 1;
     const size_t lds = (size_t)((rp - 1) * d.f + d.k) * pitch * 4;
     if (lds > (size_t)SR_LDS_BYTES) DIP_FAIL("sr_loss: the filter's source window does not fit the LDS budget");
-    hipStream_t st = (hipStream_t)stream;
     const dim3 grid(d.nblk), blk(256);
     if (d.k == 16 && d.f == 4)
         dip_launch_pair<DIP_FAM_LOSS>(sr_loss_fwd_kernel<16, 4>, sr_loss_fwd_kernel<16, 4, true>, grid, blk, lds, st, d, qn, pitch, rp);
     else
         dip_launch_pair<DIP_FAM_LOSS>(sr_loss_fwd_kernel<0, 0>, sr_loss_fwd_kernel<0, 0, true>, grid, blk, lds, st, d, qn, pitch, rp);
     DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_sr_loss_fwd(const DipSRLossDesc* dp, void* stream) {
+    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
+    const DipSRLossDesc& d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sr_fwd_launch(d, st)) return rc;
     // (through the pair as well: launched bare it would reduce instance 0 only)
-    dip_launch_pair<DIP_FAM_LOSS>(loss_reduce_kernel<false>, loss_reduce_kernel<true>, dim3(1), blk, 0, st, (const float*)d.partials,
+    dip_launch_pair<DIP_FAM_LOSS>(loss_reduce_kernel<false>, loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, (const float*)d.partials,
                                   d.nblk, 1.0 / ((double)d.C * (double)d.Ho * (double)d.Wo), d.loss);
     DIP_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int dip_sr_loss_bwd(const DipSRLossDesc* dp, const float* gscale, float* dy, int Cy, void* stream) {
-    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
-    const DipSRLossDesc& d = *dp;
-    if (dy == nullptr) DIP_FAIL("sr_loss_bwd: NULL dy");
-    if (Cy < d.C || (Cy & 3)) DIP_FAIL("sr_loss_bwd: Cy must be a multiple of 4 covering C");
-    if ((long long)d.H * d.W * Cy > 0x7fffffffLL) DIP_FAIL("sr_loss_bwd: image too large");
+// TV: whether a and b of the tile fit the budget beside the staged LR pixels (DipSRLossDesc: tvb = 0)
+template <bool TV, class D>
+static int sr_bwd_launch(const D& dd, const DipSRLossDesc& d, const float* gscale, float* dy, int Cy, int tv_mode, hipStream_t st) {
     // LR rows (columns) a 16-row tile of HR pixels can reach: its padded-domain span is at most 15 + 2 pad (a tile that
     // touches both edges), and floor(tmax / f) - ceil((tmin - k + 1) / f) + 1 <= (tmax - tmin + k - 1) / f + 1 (+ 1 to spare)
     const long long nl = (SR_T - 1 + 2 * d.pad + d.k - 1) / d.f + 2;
-    const long long lds = ((long long)d.C * nl * nl + (long long)d.k * d.k) * 4;
+    const long long tvb = TV ? 2LL * d.C * TV_P * TV_P * 4 : 0;
+    const long long lds = ((long long)d.C * nl * nl + (long long)d.k * d.k) * 4 + tvb;
     const dim3 grid(dip_cdiv(d.W, SR_T), dip_cdiv(d.H, SR_T));
-    hipStream_t st = (hipStream_t)stream;
     const dim3 blk(256);
     if (lds > SR_LDS_BYTES)
-        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<false, 0, 0>, sr_loss_bwd_kernel<false, 0, 0, true>, grid, blk, 0, st,
-                                      d, gscale, dy, Cy);
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<false, 0, 0, TV>, sr_loss_bwd_kernel<false, 0, 0, TV, true>, grid, blk, 0, st,
+                                      dd, gscale, dy, Cy, tv_mode);
     else if (d.k == 16 && d.f == 4)
-        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 16, 4>, sr_loss_bwd_kernel<true, 16, 4, true>, grid, blk, (size_t)lds,
-                                      st, d, gscale, dy, Cy);
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 16, 4, TV>, sr_loss_bwd_kernel<true, 16, 4, TV, true>, grid, blk,
+                                      (size_t)lds, st, dd, gscale, dy, Cy, tv_mode);
     else
-        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 0, 0>, sr_loss_bwd_kernel<true, 0, 0, true>, grid, blk, (size_t)lds,
-                                      st, d, gscale, dy, Cy);
+        dip_launch_pair<DIP_FAM_LOSS>(sr_loss_bwd_kernel<true, 0, 0, TV>, sr_loss_bwd_kernel<true, 0, 0, TV, true>, grid, blk,
+                                      (size_t)lds, st, dd, gscale, dy, Cy, tv_mode);
     DIP_CHECK_LAUNCH();
     return 0;
+}
+
+static const char* sr_bwd_refusal(const DipSRLossDesc& d, const float* dy, int Cy) {
+    if (dy == nullptr) return "sr_loss_bwd: NULL dy";
+    if (Cy < d.C || (Cy & 3)) return "sr_loss_bwd: Cy must be a multiple of 4 covering C";
+    if ((long long)d.H * d.W * Cy > 0x7fffffffLL) return "sr_loss_bwd: image too large";
+    return nullptr;
+}
+
+extern "C" int dip_sr_loss_bwd(const DipSRLossDesc* dp, const float* gscale, float* dy, int Cy, void* stream) {
+    if (const char* why = sr_loss_refusal(dp)) DIP_FAIL(why);
+    if (const char* why = sr_bwd_refusal(*dp, dy, Cy)) DIP_FAIL(why);
+    return sr_bwd_launch<false>(*dp, *dp, gscale, dy, Cy, 0, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------- ... with the TV term
+extern "C" int dip_sr_tv_nblk(int C, int H, int W) {
+    if (C < 1 || H < 1 || W < 1) return 0;
+    return C * dip_cdiv(H, TV_BH) * dip_cdiv(W, TV_BW);
+}
+
+// everything the two TV entry points refuse before a launch; *mode: the exact form of s^beta
+static const char* sr_tv_refusal(const DipSRTVDesc* dp, int* mode) {
+    if (dp == nullptr) return "sr_tv_loss: NULL descriptor";
+    if (const char* why = sr_loss_refusal(&dp->sr)) return why;
+    const DipSRTVDesc& d = *dp;
+    if (d.tv_weight == nullptr || d.tv_partials == nullptr) return "sr_tv_loss: NULL tv_weight / tv_partials";
+    if (d.tv_nblk != dip_sr_tv_nblk(d.sr.C, d.sr.H, d.sr.W)) return "sr_tv_loss: tv_nblk must come from dip_sr_tv_nblk";
+    if (!(d.beta > 0.f) || !(d.beta <= 3.402823466e38f)) return "sr_tv_loss: beta must be finite and > 0";
+    *mode = d.beta == 0.5f ? TV_SQRT : d.beta == 1.f ? TV_ONE : d.beta == 2.f ? TV_TWO : TV_POW;
+    return nullptr;
+}
+
+extern "C" int dip_sr_tv_loss_fwd(const DipSRTVDesc* dp, void* stream) {
+    int mode = 0;
+    if (const char* why = sr_tv_refusal(dp, &mode)) DIP_FAIL(why);
+    const DipSRTVDesc& d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sr_fwd_launch(d.sr, st)) return rc;
+    dip_launch_pair<DIP_FAM_LOSS>(sr_tv_fwd_kernel<false>, sr_tv_fwd_kernel<true>, dim3(d.tv_nblk), dim3(256), 0, st, d, mode);
+    DIP_CHECK_LAUNCH();
+    dip_launch_pair<DIP_FAM_LOSS>(sr_tv_reduce_kernel<false>, sr_tv_reduce_kernel<true>, dim3(1), dim3(256), 0, st, d);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_sr_tv_loss_bwd(const DipSRTVDesc* dp, const float* gscale, float* dy, int Cy, void* stream) {
+    int mode = 0;
+    if (const char* why = sr_tv_refusal(dp, &mode)) DIP_FAIL(why);
+    if (const char* why = sr_bwd_refusal(dp->sr, dy, Cy)) DIP_FAIL(why);
+    return sr_bwd_launch<true>(*dp, dp->sr, gscale, dy, Cy, mode, (hipStream_t)stream);
 }

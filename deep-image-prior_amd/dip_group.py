@@ -30,6 +30,14 @@ different taps of one (k, factor, pad); there is no mask.
     g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, reg_noise_std=0.03)
     g.out, g.out_LR                 # [B, C, H, W] HR outputs, [B, C, Ho, Wo] their down-sampled versions
 
+`tv_weights=` adds the TV prior of the same closure (total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR);
+super-resolution.ipynb:180-181, sr_prior_effect.ipynb:109): the tail of SRHead(tv_weight=) -- dip_head_fwd, dip_sr_tv_loss_fwd,
+dip_sr_tv_loss_bwd -- with the weight ONE float of every instance's slab, so a TV-weight sweep over one image is one group:
+
+    g = GroupedFits(nets, net_inputs, [img_LR] * B, downsamplers=downs, tv_weights=[1e-7, 1e-6, 1e-5], tv_beta=0.5)
+
+One float serves all instances; None or all zeros is the group above; zero and positive weights do not mix.
+
 The rest of the denoising / restoration closure (denoising.ipynb:214-248, restoration.ipynb:192-211: the exponential average
 of the output, three PSNRs, the parameter checkpoint and the 5 dB fall-back), per fit and with no Python between the iterations:
 `monitor=utils.fit_monitor.GroupedFitMonitor(imgs_gt, ...)`.  The monitor's state -- gt, out_avg, partial sums, records, state,
@@ -105,7 +113,7 @@ class GroupedFits:
     ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
-                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None):
+                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
@@ -115,12 +123,16 @@ class GroupedFits:
         monitor: None, or a utils.fit_monitor.GroupedFitMonitor: EMA, PSNR records and back-tracking per instance, inside
         the launch list (then exp_weight / ema_init stay at their defaults: the monitor carries the weight and starts from
         the first output, as FitMonitor does); with downsamplers= a utils.fit_monitor.GroupedSRFitMonitor: the psnr_LR /
-        psnr_HR record per instance (no moving average: exp_weight / ema_init stay at their defaults, out_avg stays None)."""
+        psnr_HR record per instance (no moving average: exp_weight / ema_init stay at their defaults, out_avg stays None).
+        tv_weights (with downsamplers= only): None, one float for all instances or B floats -- total_loss = mse(out_LR, img_LR)
+        + tv_weights[b] * tv_loss(out_HR, tv_beta), the tail of SRHead(tv_weight=); all zero = None; a mix of zero and positive
+        weights is refused (an instance with weight 0 on the TV path would differ from its solo fit where s == 0)."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
         self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
+        self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
             raise RuntimeError("dip-amd: GroupedFits needs nets built by models.skip.skip()")
@@ -209,6 +221,8 @@ class GroupedFits:
                         self._inst(ex["mask"], b).copy_(self._mask4(masks[b]).to(device).float().reshape(-1))
                     if self.downsamplers is not None:
                         self._inst(ex["taps"], b).copy_(self.downsamplers[b]._taps.detach().to(device).float().reshape(-1))
+                    if self.tv_weights is not None:
+                        self._inst(ex["tv_weight"], b).fill_(self.tv_weights[b])
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
                     if ex.get("mon_gt") is not None:
                         self._inst(ex["mon_gt"], b).copy_(self.monitor.imgs_gt[b].detach().to(device).float().reshape(-1))
@@ -272,6 +286,39 @@ class GroupedFits:
         else:
             monitor._check_targets(targets)
         return monitor
+
+    @staticmethod
+    def _check_tv(tv_weights, tv_beta, B, downsamplers):
+        """(the B weights or None = no TV term, tv_beta): the rule of SRHead(tv_weight=, tv_beta=), per instance."""
+        from utils.loss_head import sr_check_tv
+        if tv_weights is None:
+            return None, float(tv_beta)
+        if downsamplers is None:
+            raise ValueError("dip-amd: GroupedFits: tv_weights= belongs to the super-resolution closure: it needs downsamplers=")
+        ws = list(tv_weights) if isinstance(tv_weights, (list, tuple)) or hasattr(tv_weights, "__len__") else [tv_weights] * B
+        if len(ws) != B:
+            raise ValueError(f"GroupedFits: tv_weights is None, one float or one per instance: got {len(ws)} for {B} nets")
+        beta = float(tv_beta)
+        ws = [sr_check_tv(w, tv_beta, who="GroupedFits")[0] for w in ws]
+        if all(w == 0 for w in ws):
+            return None, beta
+        if any(w == 0 for w in ws):
+            raise ValueError(f"dip-amd: GroupedFits: tv_weights mixes zero and positive weights ({ws}): one launch list serves "
+                             "either the TV tail or the plain one; fit the instances without TV in a group of their own")
+        return ws, beta
+
+    def set_tv_weights(self, tv_weights):
+        """Other positive weights for the iterations that follow (SRHead.set_tv_weight per instance): the device scalars are
+        rewritten in stream order; the launch list and a captured hipGraph stay as they are."""
+        if self.tv_weights is None:
+            raise ValueError("dip-amd: GroupedFits.set_tv_weights on a group without a TV term: construct a new group")
+        ws, _ = self._check_tv(tv_weights, self.tv_beta, self.B, self.downsamplers)
+        if ws is None:
+            raise ValueError("dip-amd: GroupedFits.set_tv_weights: switching the TV term off changes the launch list; construct "
+                             "a new group")
+        for b, w in enumerate(ws):
+            self._inst(self._row0_extra["tv_weight"], b).fill_(w)
+        self.tv_weights = ws
 
     @staticmethod
     def _check_downsamplers(downsamplers, B, masks):
@@ -435,6 +482,11 @@ class GroupedFits:
         ex["y"] = slab.alloc(Cn * Ho * Wo)                  # out_LR
         self.nblk = self.lib.dip_sr_loss_nblk(Cn, Ho, Wo)
         ex["partials"] = slab.alloc(self.nblk)
+        tv = self.tv_weights is not None
+        if tv:                                              # two more per-instance rows: the weight and the TV partials
+            self.tv_nblk = self.lib.dip_sr_tv_nblk(Cn, eng.Hout, eng.Wout)
+            ex["tv_weight"] = slab.alloc(1)
+            ex["tv_partials"] = slab.alloc(self.tv_nblk)
         ex["loss"] = slab.alloc(1, zero=True)
         ex["gl"] = slab.alloc(1)
         ex["gl"].fill_(1.0)
@@ -446,8 +498,14 @@ class GroupedFits:
         self._head = LH.sr_descriptor(eng, geom, ex["out"].data_ptr(), ex["taps"].data_ptr(), ex["target"].data_ptr(),
                                       ex["y"].data_ptr(), ex["partials"].data_ptr(), self.nblk, ex["loss"].data_ptr())
         self._with_out_conv = True         # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
-        self._head_fwd = LH.sr_fwd_launches(eng, self._head)
-        self._head_bwd = LH.sr_bwd_launches(eng, self._head, ex["gl"].data_ptr())
+        if tv:
+            self._head = LH.sr_tv_descriptor(eng, self._head, ex["tv_weight"].data_ptr(), ex["tv_partials"].data_ptr(),
+                                             self.tv_nblk, self.tv_beta)
+            self._head_fwd = LH.sr_tv_fwd_launches(eng, self._head)
+            self._head_bwd = LH.sr_tv_bwd_launches(eng, self._head, ex["gl"].data_ptr())
+        else:
+            self._head_fwd = LH.sr_fwd_launches(eng, self._head)
+            self._head_bwd = LH.sr_bwd_launches(eng, self._head, ex["gl"].data_ptr())
         if self.monitor is not None:
             self._build_row0_sr_monitor(slab)
 

@@ -112,6 +112,15 @@ class DipSRLossDesc(C.Structure):
                 ("pad", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("sigmoid", C.c_int32)]
 
 
+class DipSRTVDesc(C.Structure):
+    _fields_ = [("sr", DipSRLossDesc), ("tv_weight", C.c_void_p), ("tv_partials", C.c_void_p), ("tv_nblk", C.c_int32),
+                ("beta", C.c_float)]
+
+    # what the callers of a head's descriptor read and rewrite (dip_optim.NativeIteration: the loss slot of the iteration)
+    loss = property(lambda self: self.sr.loss, lambda self, v: setattr(self.sr, "loss", v))
+    out = property(lambda self: self.sr.out)
+
+
 class DipFitMonitorDesc(C.Structure):
     _fields_ = [("out", C.c_void_p), ("noisy", C.c_void_p), ("gt", C.c_void_p), ("out_avg", C.c_void_p), ("n", C.c_int64),
                 ("exp_weight", C.c_float), ("backtrack_db", C.c_float), ("loss", C.c_void_p), ("partial", C.c_void_p),
@@ -261,6 +270,9 @@ _SIGS = {
     "dip_sr_loss_nblk": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dip_sr_loss_fwd": (C.c_int, [C.POINTER(DipSRLossDesc), C.c_void_p]),
     "dip_sr_loss_bwd": (C.c_int, [C.POINTER(DipSRLossDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dip_sr_tv_nblk": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "dip_sr_tv_loss_fwd": (C.c_int, [C.POINTER(DipSRTVDesc), C.c_void_p]),
+    "dip_sr_tv_loss_bwd": (C.c_int, [C.POINTER(DipSRTVDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dip_fit_monitor_nblk": (C.c_int, [C.c_int64]),
     "dip_fit_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),

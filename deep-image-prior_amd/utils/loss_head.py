@@ -30,6 +30,16 @@ Super-resolution (super-resolution.ipynb:169-186 of the reference):
 MSE (dip_sr_loss_fwd); `backward()` starts from dip_sr_loss_bwd (MSE backward + the down-sampler's adjoint + the sigmoid
 factor) instead of three autograd nodes.
 
+With the TV prior (super-resolution.ipynb:180-181, sr_prior_effect.ipynb:109):
+
+    total_loss = mse(out_LR, img_LR_var) + tv_weight * tv_loss(out_HR)
+
+    head = SRHead(net, img_LR_var, downsampler, tv_weight=tv_weight)          # tv_beta=0.5 as utils.sr_utils.tv_loss
+
+the same two calls become dip_sr_tv_loss_fwd (one more streaming kernel over out_HR; both sums reduced in one launch) and
+dip_sr_tv_loss_bwd (ONE kernel: the gather above + the TV gradient of the same pixel).  No epsilon, as in the reference: for
+tv_beta < 1 a pixel whose right and lower neighbours equal it gives NaN gradients in both spellings.
+
 Both heads describe their launches ONCE, as the (fn, args, name) triples SkipEngine.forward / backward issue one by one and
 dip_optim.NativeIteration compiles into its command arrays: `with_out_conv`, `_descriptor`, `fwd_launches`, `bwd_launches`.
 """
@@ -148,6 +158,38 @@ def sr_descriptor(eng, geom, out_ptr, taps_ptr, target_ptr, y_ptr, partials_ptr,
                            k, f, pad, Ho, Wo, 1 if eng.need_sigmoid else 0)
 
 
+def sr_check_tv(tv_weight, tv_beta, who="SRHead"):
+    """(tv_weight, tv_beta) as floats; a negative or non-finite weight and tv_beta <= 0 (or non-finite) are refused."""
+    import math
+    try:
+        w, beta = float(tv_weight), float(tv_beta)
+    except (TypeError, ValueError):
+        raise TypeError(f"dip-amd: {who}: tv_weight / tv_beta must be numbers, got {tv_weight!r} / {tv_beta!r}") from None
+    if not math.isfinite(w) or w < 0:
+        raise ValueError(f"dip-amd: {who}: tv_weight must be finite and >= 0, got {tv_weight!r}")
+    if not math.isfinite(beta) or beta <= 0:
+        raise ValueError(f"dip-amd: {who}: tv_beta must be finite and > 0, got {tv_beta!r}")
+    return w, beta
+
+
+def sr_tv_descriptor(eng, sr_desc, tv_weight_ptr, tv_partials_ptr, tv_nblk, beta):
+    """DipSRTVDesc: the DipSRLossDesc of the same fit + the TV term's device scalar, partials and beta."""
+    return N.DipSRTVDesc(sr_desc, tv_weight_ptr, tv_partials_ptr, tv_nblk, beta)
+
+
+def sr_tv_fwd_launches(eng, desc):
+    """dip_head_fwd + dip_sr_tv_loss_fwd: total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR, beta)."""
+    Cs = N.round_up(eng.n_out, 4)
+    return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.sr.out, eng.n_out, eng.Hout * eng.Wout, Cs,
+                                    1 if eng.need_sigmoid else 0), "head_fwd"),
+            (eng.lib.dip_sr_tv_loss_fwd, (C.byref(desc),), "sr_tv_loss_fwd")]
+
+
+def sr_tv_bwd_launches(eng, desc, gscale_ptr):
+    return [(eng.lib.dip_sr_tv_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
+             "sr_tv_loss_bwd")]
+
+
 def sr_fwd_launches(eng, desc):
     """dip_head_fwd (NHWC -> NCHW + sigmoid: out_HR as net(x) writes it) + dip_sr_loss_fwd, as (fn, args, name) triples."""
     Cs = N.round_up(eng.n_out, 4)
@@ -163,11 +205,17 @@ def sr_bwd_launches(eng, desc, gscale_ptr):
 
 class SRHead:
     """net + fixed-taps Downsampler + MSE (see the module docstring).  `target` (img_LR) may be replaced and the
-    down-sampler's state reloaded between calls; `out_LR` is a buffer this object owns and overwrites."""
+    down-sampler's state reloaded between calls; `out_LR` is a buffer this object owns and overwrites.
+    tv_weight > 0: total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR, tv_beta) (dip_sr_tv_loss_fwd / _bwd); the
+    weight lives in a device scalar, rewritten by set_tv_weight() without a re-plan."""
     kind = "sr"
     with_out_conv = True        # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
 
-    def __init__(self, net, img_LR, downsampler):
+    def __init__(self, net, img_LR, downsampler, tv_weight=0.0, tv_beta=0.5):
+        self.tv_weight, self.tv_beta = sr_check_tv(tv_weight, tv_beta)
+        self._tv = self.tv_weight > 0
+        self._tvw = None            # the device scalar; a new one when the weight is first needed on another device
+        self._tv_scratch = None
         from models.downsampler import Downsampler
         eng = getattr(net, "__dict__", {}).get("_dip_engine")
         if eng is None or isinstance(eng, Exception):
@@ -221,22 +269,44 @@ class SRHead:
         if self._y is None or tuple(self._y.shape) != (1, Cn, Ho, Wo) or self._y.device != dev:
             self._y = torch.empty((1, Cn, Ho, Wo), dtype=torch.float32, device=dev)
         self._keep = (out.detach(), taps)
-        return sr_descriptor(eng, (k, f, pad, Ho, Wo), out.data_ptr(), taps.data_ptr(), self.target.data_ptr(), self._y.data_ptr(),
-                             self._scratch.data_ptr(), nblk, loss.data_ptr())
+        sr = sr_descriptor(eng, (k, f, pad, Ho, Wo), out.data_ptr(), taps.data_ptr(), self.target.data_ptr(), self._y.data_ptr(),
+                           self._scratch.data_ptr(), nblk, loss.data_ptr())
+        if not self._tv:
+            return sr
+        tv_nblk = eng.lib.dip_sr_tv_nblk(Cn, eng.Hout, eng.Wout)
+        if self._tv_scratch is None or self._tv_scratch.numel() != tv_nblk or self._tv_scratch.device != dev:
+            self._tv_scratch = torch.empty(tv_nblk, dtype=torch.float32, device=dev)
+        if self._tvw is None or self._tvw.device != dev:
+            self._tvw = torch.full((1,), self.tv_weight, dtype=torch.float32, device=dev)
+        return sr_tv_descriptor(eng, sr, self._tvw.data_ptr(), self._tv_scratch.data_ptr(), tv_nblk, self.tv_beta)
+
+    def set_tv_weight(self, w):
+        """Another tv_weight > 0 for the calls that follow: the device scalar is rewritten in stream order, nothing is
+        re-planned (a NativeIteration keeps its command arrays).  To or from 0 the launch list would change: build a new head."""
+        w, _ = sr_check_tv(w, self.tv_beta)
+        if (w > 0) != self._tv:
+            raise ValueError(f"dip-amd: SRHead.set_tv_weight({w!r}) on a head built with tv_weight={self.tv_weight!r}: switching "
+                             "the TV term on or off changes the launch list; construct a new SRHead")
+        self.tv_weight = w
+        if self._tvw is not None:
+            self._tvw.fill_(w)
 
     def fwd_launches(self, eng, desc):
-        return sr_fwd_launches(eng, desc)
+        return sr_tv_fwd_launches(eng, desc) if self._tv else sr_fwd_launches(eng, desc)
 
     def bwd_launches(self, eng, desc, gscale_ptr):
-        return sr_bwd_launches(eng, desc, gscale_ptr)
+        return sr_tv_bwd_launches(eng, desc, gscale_ptr) if self._tv else sr_bwd_launches(eng, desc, gscale_ptr)
 
     def _plan_key(self):
         d = self.downsampler
-        return (self.kind, id(self.target), self.target.data_ptr(), id(d), id(d._taps), int(d.kernel.shape[0]), int(d.factor),
-                int(d._pad), id(self._y))
+        key = (self.kind, id(self.target), self.target.data_ptr(), id(d), id(d._taps), int(d.kernel.shape[0]), int(d.factor),
+               int(d._pad), id(self._y))
+        # (the weight's VALUE is not part of the key: it is read from the device scalar when the kernels run)
+        return key + (("tv", self.tv_beta, id(self._tvw), id(self._tv_scratch)) if self._tv else ())
 
     def _plan_keep(self):
-        return (self.target, self.downsampler, self._keep, self._scratch, self._y)
+        return (self.target, self.downsampler, self._keep, self._scratch, self._y) + \
+            ((self._tvw, self._tv_scratch) if self._tv else ())
 
     def __call__(self, net_input):
         import dip_engine

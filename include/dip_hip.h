@@ -652,6 +652,42 @@ int dip_sr_loss_nblk(int C, int Ho, int Wo);
 int dip_sr_loss_fwd(const DipSRLossDesc* d, void* stream);
 int dip_sr_loss_bwd(const DipSRLossDesc* d, const float* gscale, float* dy, int Cy, void* stream);
 
+/* ... with the TV term of the closure (super-resolution.ipynb:180-181, sr_prior_effect.ipynb:109):
+ *   total_loss = mse(out_LR, img_LR_var) + tv_weight * tv_loss(out_HR, beta)
+ * tv_loss (utils/sr_utils.py:84-94 of the reference) has, per channel, one term per pixel with y < H-1 and x < W-1:
+ *   dhd = out[y][x+1] - out[y][x];  dwd = out[y+1][x] - out[y][x];  s = fmaf(dhd, dhd, dwd * dwd);  term = s^beta
+ * s^beta is sqrtf(s), s, s * s for beta 0.5, 1, 2 (the exact forms ATen's pow has) and powf(s, beta) otherwise.
+ *   forward : y and the MSE partials come from the kernel dip_sr_loss_fwd launches (y stays bit-identical to
+ *             dip_lanczos_down_fwd(out)); one more kernel streams over out (one channel's 16 rows x 64 columns per block: a
+ *             chain of fp32 adds in row order per lane, an LDS tree per block, one fp32 partial per block, no float atomics);
+ *             one reduce launch sums both partial ranges in fixed order in fp64 and writes
+ *             *loss = (float)(sum_mse / (C*Ho*Wo) + (double)*tv_weight * sum_tv).   H == 1 or W == 1: sum_tv = 0.
+ *   backward: ONE kernel: acc = the gather of dip_sr_loss_bwd (same fmaf chain), plus the TV gradient of the same pixel.  With
+ *             g(s) = beta * s^(beta-1) (0.5f / sqrtf(s), 1.f, 2.f * s for beta 0.5, 1, 2; beta * powf(s, beta - 1.f) otherwise),
+ *             a = g(s) * dhd, b = g(s) * dwd of the term at a pixel -- both 0.f where the term does not exist (the last row, the
+ *             last column) -- the evaluation order, every operation rounded on its own (no contraction), is
+ *               t    = ((-(a[p] + b[p])) + a[left of p]) + b[above p]
+ *               coef = (2.f * *tv_weight) * gs                         (gs = gscale ? *gscale : 1.f)
+ *               g    = acc + coef * t;      dy[p][c] = sigmoid ? g * ((1.f - out) * out) : g
+ *             the same order whether a and b are staged in LDS (17 x 17 per channel per 16 x 16 tile) or formed where they are
+ *             read (a filter whose staged form would pass the 48 KB LDS budget), solo or grouped.
+ * There is NO epsilon and no guard at s == 0, as in the reference: for beta < 1 g(0) = +inf and a = inf * 0 = NaN, which is what
+ * autograd over the spelled closure yields at a pixel whose right and lower neighbours equal it; beta >= 1 stays finite.
+ * tv_weight is ONE float in device memory: the instances of a group may differ in it and it may be rewritten between calls
+ * without re-planning.  Refused with -1 before any launch: everything dip_sr_loss_fwd / _bwd refuse (on `sr`), NULL tv_weight
+ * or tv_partials, tv_nblk != dip_sr_tv_nblk(C, H, W), beta <= 0 or not finite.  Inside dip_group_begin / dip_group_end:
+ * as DipSRLossDesc, with tv_weight and tv_partials in instance 0's slab too.  sizeof(DipSRTVDesc) == 120 (LP64). */
+typedef struct DipSRTVDesc {
+    DipSRLossDesc sr;        /* everything dip_sr_loss_fwd / _bwd read and write */
+    const float* tv_weight;  /* 1 float, device memory */
+    float* tv_partials;      /* tv_nblk floats */
+    int tv_nblk;             /* dip_sr_tv_nblk(C, H, W) */
+    float beta;              /* > 0; the notebooks' 0.5 */
+} DipSRTVDesc;
+int dip_sr_tv_nblk(int C, int H, int W);
+int dip_sr_tv_loss_fwd(const DipSRTVDesc* d, void* stream);
+int dip_sr_tv_loss_bwd(const DipSRTVDesc* d, const float* gscale, float* dy, int Cy, void* stream);
+
 /* ---------------------------------------------------------------- closure bookkeeping ---- */
 /* The per-iteration bookkeeping of the notebooks' closures without host round trips
  * (denoising.ipynb:214-248): EMA of the output, PSNR against the noisy / clean image, and the
