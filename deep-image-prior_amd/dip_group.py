@@ -210,46 +210,35 @@ class GroupedFits:
             rows = self.mem.view(B, self.stride)
             if B > 1:
                 rows[1:].copy_(rows[:1].expand(B - 1, self.stride))
-            ex = self._row0_extra
+            ex, mon = self._row0_extra, self.monitor
+            own = (("saved", lambda b: net_inputs[b]), ("target", lambda b: targets[b]), ("mask", lambda b: self._mask4(masks[b])),
+                   ("taps", lambda b: self.downsamplers[b]._taps), ("mon_gt", lambda b: mon.imgs_gt[b]),
+                   ("mon_hr", lambda b: mon.imgs_HR[b]))
             with torch.no_grad():
                 for b in range(B):
                     if b > 0:
                         self._adopt_net(b)
-                    self._inst(ex["saved"], b).copy_(net_inputs[b].detach().to(device).float().reshape(-1))
-                    self._inst(ex["target"], b).copy_(targets[b].detach().to(device).float().reshape(-1))
-                    if ex["mask"] is not None:
-                        self._inst(ex["mask"], b).copy_(self._mask4(masks[b]).to(device).float().reshape(-1))
-                    if self.downsamplers is not None:
-                        self._inst(ex["taps"], b).copy_(self.downsamplers[b]._taps.detach().to(device).float().reshape(-1))
+                    for k, src in own:                       # the instance's own data, where row 0 has such a buffer
+                        if ex.get(k) is not None:
+                            self._inst(ex[k], b).copy_(src(b).detach().to(device).float().reshape(-1))
                     if self.tv_weights is not None:
                         self._inst(ex["tv_weight"], b).fill_(self.tv_weights[b])
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
-                    if ex.get("mon_gt") is not None:
-                        self._inst(ex["mon_gt"], b).copy_(self.monitor.imgs_gt[b].detach().to(device).float().reshape(-1))
-                    if ex.get("mon_hr") is not None:
-                        self._inst(ex["mon_hr"], b).copy_(self.monitor.imgs_HR[b].detach().to(device).float().reshape(-1))
             # --- what the caller reads: strided views over the instances
-            HWo = eng.Hout * eng.Wout
-            self.losses = self._strided(ex["loss"], (B,), ())
-            self.out = self._strided(ex["out"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1))
-            self.out_avg = torch.zeros((B, oc.Cout, eng.Hout, eng.Wout), dtype=torch.float32, device=device) \
-                if self.exp_weight is not None else None
-            if self.monitor is not None and self.downsamplers is not None:
-                self.monitor._adopt(self, self._strided(ex["mon_records"], (B, self.monitor.capacity, 5), (5, 1)),
-                                    self._strided(ex["mon_counter"], (B,), ()))
-            elif self.monitor is not None:
-                cap = self.monitor.capacity
-                self.monitor._adopt(self, self._strided(ex["mon_records"], (B, cap, 8), (8, 1)),
-                                    self._strided(ex["mon_state"], (B, 4), (1,)), self._strided(ex["mon_counter"], (B,), ()),
-                                    self._strided(ex["mon_avg"], (B, oc.Cout, eng.Hout, eng.Wout), (HWo, eng.Wout, 1)),
-                                    None if ex["mon_snapshot"] is None
-                                    else self._strided(ex["mon_snapshot"], (B, eng.n_arena), (1,)))
-                self.out_avg = self.monitor.out_avg
-            self.out_LR = None
-            if self.downsamplers is not None:
-                _, _, _, Ho, Wo = self._sr_geom
-                self.out_LR = self._strided(ex["y"], (B, oc.Cout, Ho, Wo), (Ho * Wo, Wo, 1))
-            self._nbt_all = self._strided(eng.nbt, (B, eng.nbt.numel()), (1,))
+            hr = (oc.Cout, eng.Hout, eng.Wout)
+            self.losses = self._strided(ex["loss"])
+            self.out = self._strided(ex["out"], *hr)
+            self.out_LR = self._strided(ex.get("y"), *t0.shape[1:])
+            self.out_avg = torch.zeros((B,) + hr, dtype=torch.float32, device=device) if self.exp_weight is not None else None
+            if mon is not None:
+                views = dict(records=self._strided(ex["mon_records"], mon.capacity, len(mon.COLUMNS)),
+                             counter=self._strided(ex["mon_counter"]))
+                if self.downsamplers is None:
+                    self.out_avg = self._strided(ex["mon_avg"], *hr)
+                    views.update(state=self._strided(ex["mon_state"], 4), out_avg=self.out_avg,
+                                 snapshot=self._strided(ex["mon_snapshot"], eng.n_arena))
+                mon._adopt(self, **views)
+            self._nbt_all = self._strided(eng.nbt, eng.nbt.numel())
             if not self._dry:
                 torch.cuda.synchronize(device)
 
@@ -282,7 +271,7 @@ class GroupedFits:
             raise RuntimeError(f"dip-amd: this {type(monitor).__name__} already belongs to a GroupedFits (a monitor is adopted "
                                "once)")
         if sr:
-            monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _build_row0_sr_monitor)
+            monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _build_row0_monitor)
         else:
             monitor._check_targets(targets)
         return monitor
@@ -361,17 +350,18 @@ class GroupedFits:
             for fn, args, name in ops:
                 for k, a in enumerate(args):
                     visit(name, f"arg{k}", a._obj if hasattr(a, "_obj") else a)
-        visit("sr_loss" if self.downsamplers is not None else "loss_head", "desc", self._head)
-        for fn, args, name in self._head_fwd + self._head_bwd:      # pointer ARGUMENTS of the head's launches (y_out, gl, dy_out)
-            for k, a in enumerate(args):
-                if not hasattr(a, "_obj"):
-                    visit(name, f"arg{k}", a)
-        if self.monitor is not None:
-            visit("fit_monitor", "desc", self._mdesc)
-            for fn, args, name in self._mon:
+
+        def pointer_args(ops):          # of launches whose descriptor is visited on its own (the head's: y_out, gl, dy_out)
+            for fn, args, name in ops:
                 for k, a in enumerate(args):
                     if not hasattr(a, "_obj"):
                         visit(name, f"arg{k}", a)
+
+        visit("sr_loss" if self.downsamplers is not None else "loss_head", "desc", self._head)
+        pointer_args(self._head_fwd + self._head_bwd)
+        if self.monitor is not None:
+            visit("fit_monitor", "desc", self._mdesc)
+            pointer_args(self._mon)
         for k, t in self._row0_extra.items():
             if t is not None:
                 visit("extra", k, t.data_ptr())
@@ -390,30 +380,47 @@ class GroupedFits:
         return m.contiguous()
 
     def _build_row0(self, slab, Cimg, H, W, t0, m0):
-        """Everything instance 0 owns, in a fixed order, from `slab`."""
-        eng = self.eng
+        """Everything instance 0 owns, in a fixed order, from `slab`: the engine's buffers, the closure's input, the loss head's
+        buffers -- those of utils.loss_head.MSEHead, or of SRHead -- with its descriptor and launches, the closure's end and,
+        behind everything else, the monitor's buffers."""
+        from utils import loss_head as LH
+        eng, lib, sr, tv = self.eng, self.lib, self.downsamplers is not None, self.tv_weights is not None
         eng.slab = slab
-        dev = self.device
-        eng._build_arenas(dev)
+        eng._build_arenas(self.device)
         if Cimg != eng.sc[0].down_a.Cin:
             raise RuntimeError(f"dip-amd: input has {Cimg} channels, net expects {eng.sc[0].down_a.Cin}")
         eng._build_plan(H, W, Cimg)
-        if self.downsamplers is not None:
-            return self._build_row0_sr(slab, Cimg, H, W, t0)
-        if (eng.Hout, eng.Wout) != tuple(t0.shape[2:]):
-            raise ValueError(f"GroupedFits: targets are {tuple(t0.shape[2:])}, the net output is {(eng.Hout, eng.Wout)}")
-        oc = eng.out_conv
-        nin = Cimg * H * W
-        nout = oc.Cout * eng.Hout * eng.Wout
+        Cn, Hn, Wn = eng.n_out, eng.Hout, eng.Wout
+        if sr:
+            geom = k, f, pad, Ho, Wo = LH.sr_geometry(self.downsamplers[0], Hn, Wn, who="GroupedFits")
+            if (Ho, Wo) != tuple(t0.shape[2:]):
+                raise ValueError(f"GroupedFits: targets (the LR images) are {tuple(t0.shape[2:])}, the down-sampled net output is "
+                                 f"{(Ho, Wo)} (net output {(Hn, Wn)}, k {k}, factor {f}, pad {pad})")
+        elif (Hn, Wn) != tuple(t0.shape[2:]):
+            raise ValueError(f"GroupedFits: targets are {tuple(t0.shape[2:])}, the net output is {(Hn, Wn)}")
+        nin, nout = Cimg * H * W, Cn * Hn * Wn
         ex = {}
         ex["saved"] = slab.alloc(nin)                       # net_input_saved (denoising.ipynb:198)
         ex["noisy"] = slab.alloc(nin) if self.std > 0 else None
         ex["rng"] = slab.alloc(2, torch.int64, zero=True)   # {Philox offset, seed} (dip_noise_axpy_dev2)
-        ex["target"] = slab.alloc(nout)
-        ex["mask"] = slab.alloc(self.mask_c * eng.Hout * eng.Wout) if m0 is not None else None
-        ex["out"] = slab.alloc(nout)
-        self.nblk = self.lib.dip_loss_head_nblk(eng.Hout * eng.Wout, oc.Cin)
-        ex["partials"] = slab.alloc(self.nblk)
+        if sr:
+            ex["taps"] = slab.alloc(k * k)                  # per-instance data: every pointer of a grouped launch is in the slab
+            ex["target"] = slab.alloc(Cn * Ho * Wo)         # img_LR
+            ex["mask"] = None
+            ex["out"] = slab.alloc(nout)                    # out_HR, NCHW
+            ex["y"] = slab.alloc(Cn * Ho * Wo)              # out_LR
+            self.nblk = lib.dip_sr_loss_nblk(Cn, Ho, Wo)
+            ex["partials"] = slab.alloc(self.nblk)
+            if tv:                                          # two more per-instance rows: the weight and the TV partials
+                self.tv_nblk = lib.dip_sr_tv_nblk(Cn, Hn, Wn)
+                ex["tv_weight"] = slab.alloc(1)
+                ex["tv_partials"] = slab.alloc(self.tv_nblk)
+        else:
+            ex["target"] = slab.alloc(nout)
+            ex["mask"] = slab.alloc(self.mask_c * Hn * Wn) if m0 is not None else None
+            ex["out"] = slab.alloc(nout)
+            self.nblk = lib.dip_loss_head_nblk(Hn * Wn, eng.out_conv.Cin)
+            ex["partials"] = slab.alloc(self.nblk)
         ex["loss"] = slab.alloc(1, zero=True)
         ex["gl"] = slab.alloc(1)                            # d(total_loss)/d(total_loss) = 1 (total_loss.backward())
         ex["gl"].fill_(1.0)
@@ -422,112 +429,53 @@ class GroupedFits:
         ex["iter"] = slab.alloc(16, torch.uint8, zero=True)  # DipIterState: step count, step size, sqrt(bias correction 2)
         self._row0_extra = ex
         self._x = ex["noisy"] if self.std > 0 else ex["saved"]
-        a = eng.last_act
-        ptr = lambda t, off=0: None if t is None else t.data_ptr() + 4 * off
-        self._tr = a.transform()
-        self._head = N.DipLossHeadDesc(ptr(a.buf), a.Cs, oc.Cin, self._tr, ptr(eng.params, oc.w_off),
-                                       ptr(eng.params, oc.b_off) if oc.b_off >= 0 else None, oc.Cout, eng.Hout * eng.Wout,
-                                       1 if eng.need_sigmoid else 0, ptr(ex["target"]), ptr(ex["mask"]), self.mask_c,
-                                       ptr(ex["out"]), ptr(ex["partials"]), self.nblk, ptr(ex["loss"]))
-        self._with_out_conv = False        # dip_loss_head_fwd runs the output conv itself
-        self._head_fwd = [(self.lib.dip_loss_head_fwd, (C.byref(self._head),), "loss_head_fwd")]
-        self._head_bwd = [(self.lib.dip_loss_head_bwd, (C.byref(self._head), ex["gl"].data_ptr(), eng.dy_out.data_ptr(),
-                                                        round_up(eng.n_out, 4)), "loss_head_bwd")]
+        at = lambda k: None if ex[k] is None else ex[k].data_ptr()
+        if sr:
+            self._head = LH.sr_descriptor(eng, geom, at("out"), at("taps"), at("target"), at("y"), at("partials"), self.nblk,
+                                          at("loss"))
+            if tv:
+                self._head = LH.sr_tv_descriptor(self._head, at("tv_weight"), at("tv_partials"), self.tv_nblk, self.tv_beta)
+            fwd, bwd = LH.sr_fwd_launches, LH.sr_bwd_launches
+        else:
+            self._head, self._tr = LH.mse_descriptor(eng, at("target"), at("mask"), self.mask_c, at("out"), at("partials"),
+                                                     self.nblk, at("loss"))
+            fwd, bwd = LH.mse_fwd_launches, LH.mse_bwd_launches
+        # (MSE tail: dip_loss_head_fwd runs the output conv itself; super-resolution: the forward list runs to its end and
+        # dip_head_fwd writes out_HR as net(x) does)
+        self._with_out_conv = sr
+        self._head_fwd, self._head_bwd = fwd(eng, self._head), bwd(eng, self._head, at("gl"))
         if self.monitor is not None:
-            self._build_row0_monitor(slab, nout)
+            self._build_row0_monitor(slab)
 
-    def _build_row0_monitor(self, slab, nout):
-        """The monitor's buffers, behind everything else instance 0 owns: what utils.fit_monitor.FitMonitor allocates for a
-        solo fit, as per-instance data of the slab; ONE descriptor over them (noisy = the target, out = the head's output,
-        loss = the slab's loss scalar: nothing is rewritten per iteration) and the launches of an iteration."""
-        eng, ex, m = self.eng, self._row0_extra, self.monitor
+    def _build_row0_monitor(self, slab):
+        """The monitor's buffers, behind everything else instance 0 owns: what utils.fit_monitor.FitMonitor (super-resolution:
+        SRFitMonitor) allocates for a solo fit, as per-instance data of the slab; ONE descriptor over them (the outputs = the
+        head's, noisy / img_LR = the target, loss = the slab's loss scalar: nothing is rewritten per iteration) and the
+        launches of an iteration."""
+        from utils import fit_monitor as FM
+        eng, lib, ex, m = self.eng, self.lib, self._row0_extra, self.monitor
+        nout = ex["out"].numel()
+        if self.downsamplers is not None:
+            m._check_hr(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
+            ex["mon_hr"] = slab.alloc(nout) if m.imgs_HR is not None else None
+            ex["mon_partial"] = slab.alloc(lib.dip_fit_monitor_nblk(nout) + lib.dip_fit_monitor_nblk(ex["y"].numel()))
+            ex["mon_records"] = slab.alloc(m.capacity * 5, zero=True)
+            ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
+            self._mdesc = FM.sr_monitor_descriptor(m, ex["out"], ex["y"], ex["mon_hr"], ex["target"], ex["mon_partial"],
+                                                   ex["mon_records"], ex["mon_counter"], ex["loss"])
+            self._mon = FM.sr_monitor_launches(lib, self._mdesc)
+            return
         ex["mon_gt"] = slab.alloc(nout) if m.imgs_gt is not None else None
         ex["mon_avg"] = slab.alloc(nout, zero=True)
-        ex["mon_partial"] = slab.alloc(4 * self.lib.dip_fit_monitor_nblk(nout))
+        ex["mon_partial"] = slab.alloc(4 * lib.dip_fit_monitor_nblk(nout))
         ex["mon_records"] = slab.alloc(m.capacity * 8, zero=True)
         ex["mon_state"] = slab.alloc(4, zero=True)
         ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
         ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._mdesc = N.DipFitMonitorDesc(ptr(ex["out"]), ptr(ex["target"]), ptr(ex["mon_gt"]), ptr(ex["mon_avg"]), nout,
-                                          m.exp_weight, m.backtrack_db, ptr(ex["loss"]), ptr(ex["mon_partial"]),
-                                          ptr(ex["mon_records"]), m.capacity, m.show_every, 1 if m.backtracking else 0, 0,
-                                          ptr(ex["mon_counter"]), ptr(ex["mon_state"]))
-        self._mon = [(self.lib.dip_fit_monitor_dev, (C.byref(self._mdesc),), "fit_monitor_dev")]
-        if m.backtracking:
-            self._mon.append((self.lib.dip_arena_backtrack, (eng.params.data_ptr(), ptr(ex["mon_snapshot"]), eng.n_arena,
-                                                             ptr(ex["mon_state"])), "arena_backtrack"))
-
-    def _build_row0_sr(self, slab, Cimg, H, W, t0):
-        """Row 0 of a super-resolution group: the buffers of utils.loss_head.SRHead (taps, LR target, HR output, LR output,
-        partials) in the slab, its descriptor and its launches."""
-        from utils import loss_head as LH
-        eng = self.eng
-        geom = LH.sr_geometry(self.downsamplers[0], eng.Hout, eng.Wout, who="GroupedFits")
-        k, f, pad, Ho, Wo = geom
-        if (Ho, Wo) != tuple(t0.shape[2:]):
-            raise ValueError(f"GroupedFits: targets (the LR images) are {tuple(t0.shape[2:])}, the down-sampled net output is "
-                             f"{(Ho, Wo)} (net output {(eng.Hout, eng.Wout)}, k {k}, factor {f}, pad {pad})")
-        self._sr_geom = geom
-        Cn = eng.n_out
-        nin = Cimg * H * W
-        ex = {}
-        ex["saved"] = slab.alloc(nin)
-        ex["noisy"] = slab.alloc(nin) if self.std > 0 else None
-        ex["rng"] = slab.alloc(2, torch.int64, zero=True)
-        ex["taps"] = slab.alloc(k * k)                      # per-instance data: every pointer of a grouped launch is in the slab
-        ex["target"] = slab.alloc(Cn * Ho * Wo)             # img_LR
-        ex["mask"] = None
-        ex["out"] = slab.alloc(Cn * eng.Hout * eng.Wout)    # out_HR, NCHW
-        ex["y"] = slab.alloc(Cn * Ho * Wo)                  # out_LR
-        self.nblk = self.lib.dip_sr_loss_nblk(Cn, Ho, Wo)
-        ex["partials"] = slab.alloc(self.nblk)
-        tv = self.tv_weights is not None
-        if tv:                                              # two more per-instance rows: the weight and the TV partials
-            self.tv_nblk = self.lib.dip_sr_tv_nblk(Cn, eng.Hout, eng.Wout)
-            ex["tv_weight"] = slab.alloc(1)
-            ex["tv_partials"] = slab.alloc(self.tv_nblk)
-        ex["loss"] = slab.alloc(1, zero=True)
-        ex["gl"] = slab.alloc(1)
-        ex["gl"].fill_(1.0)
-        ex["m"] = slab.alloc(eng.n_arena, zero=True)
-        ex["v"] = slab.alloc(eng.n_arena, zero=True)
-        ex["iter"] = slab.alloc(16, torch.uint8, zero=True)
-        self._row0_extra = ex
-        self._x = ex["noisy"] if self.std > 0 else ex["saved"]
-        self._head = LH.sr_descriptor(eng, geom, ex["out"].data_ptr(), ex["taps"].data_ptr(), ex["target"].data_ptr(),
-                                      ex["y"].data_ptr(), ex["partials"].data_ptr(), self.nblk, ex["loss"].data_ptr())
-        self._with_out_conv = True         # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
-        if tv:
-            self._head = LH.sr_tv_descriptor(eng, self._head, ex["tv_weight"].data_ptr(), ex["tv_partials"].data_ptr(),
-                                             self.tv_nblk, self.tv_beta)
-            self._head_fwd = LH.sr_tv_fwd_launches(eng, self._head)
-            self._head_bwd = LH.sr_tv_bwd_launches(eng, self._head, ex["gl"].data_ptr())
-        else:
-            self._head_fwd = LH.sr_fwd_launches(eng, self._head)
-            self._head_bwd = LH.sr_bwd_launches(eng, self._head, ex["gl"].data_ptr())
-        if self.monitor is not None:
-            self._build_row0_sr_monitor(slab)
-
-    def _build_row0_sr_monitor(self, slab):
-        """The super-resolution monitor's buffers, behind everything else instance 0 owns: the optional HR ground truth, the
-        partial sums, the records and the counter of utils.fit_monitor.SRFitMonitor as per-instance data of the slab; ONE
-        descriptor over them (out_HR / out_LR = the head's two outputs, img_LR = the target, loss = the slab's loss scalar:
-        nothing is rewritten per iteration) and the ONE launch of an iteration."""
-        eng, ex, m = self.eng, self._row0_extra, self.monitor
-        _, _, _, Ho, Wo = self._sr_geom
-        Cn = eng.n_out
-        m._check_hr(self.B, (1, Cn, eng.Hout, eng.Wout))
-        n_hr, n_lr = Cn * eng.Hout * eng.Wout, Cn * Ho * Wo
-        ex["mon_hr"] = slab.alloc(n_hr) if m.imgs_HR is not None else None
-        ex["mon_partial"] = slab.alloc(self.lib.dip_fit_monitor_nblk(n_hr) + self.lib.dip_fit_monitor_nblk(n_lr))
-        ex["mon_records"] = slab.alloc(m.capacity * 5, zero=True)
-        ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        self._mdesc = N.DipSRMonitorDesc(ptr(ex["out"]), ptr(ex["y"]), ptr(ex["mon_hr"]), ptr(ex["target"]), n_hr, n_lr,
-                                         ptr(ex["loss"]), ptr(ex["mon_partial"]), ptr(ex["mon_records"]), m.capacity, 0,
-                                         ptr(ex["mon_counter"]))
-        self._mon = [(self.lib.dip_sr_monitor_dev, (C.byref(self._mdesc),), "sr_monitor_dev")]
+        self._mdesc = FM.fit_monitor_descriptor(m, ex["out"], ex["target"], ex["mon_gt"], ex["mon_avg"], ex["mon_partial"],
+                                                ex["mon_records"], ex["mon_counter"], ex["mon_state"], ex["loss"])
+        self._mon = FM.fit_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena,
+                                            None if ex["mon_snapshot"] is None else ex["mon_snapshot"].data_ptr())
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()
@@ -539,13 +487,18 @@ class GroupedFits:
         o = self._off(t0) + b * self.stride
         return self.mem[o:o + t0.numel() * t0.element_size()].view(t0.dtype)
 
-    def _strided(self, t0, shape, inner_strides):
-        """[B, ...] view over the instances of t0 (row 0), without a copy."""
+    def _strided(self, t0, *shape):
+        """[B, *shape] view over the instances of t0 (row 0; None: no such buffer), without a copy."""
+        if t0 is None:
+            return None
         es = t0.element_size()
         assert self.stride % es == 0
         flat = self.mem.view(t0.dtype)
+        inner = [1] * len(shape)
+        for d in range(len(shape) - 2, -1, -1):
+            inner[d] = inner[d + 1] * shape[d + 1]
         # (as_strided's offset counts from the start of the STORAGE, not of `flat`)
-        return torch.as_strided(flat, shape, (self.stride // es,) + tuple(inner_strides),
+        return torch.as_strided(flat, (self.B,) + tuple(shape), [self.stride // es] + inner,
                                 flat.storage_offset() + self._off(t0) // es)
 
     def _adopt_net(self, b):
@@ -618,18 +571,25 @@ class GroupedFits:
             else:
                 self.out_avg.mul_(self.exp_weight).add_(self.out, alpha=1 - self.exp_weight)
 
-    def step(self, n=1):
-        """n eager iterations (launches on the current stream + the engine's auxiliary streams)."""
+    def _check_room(self, n):
+        """The monitor refuses n more iterations that do not fit its records, before anything is issued."""
         if self.monitor is not None:
             self.monitor._check_room(n)
+
+    def _issued(self, n):
+        self.iterations += n
+        if self.monitor is not None:
+            self.monitor.i += n
+
+    def step(self, n=1):
+        """n eager iterations (launches on the current stream + the engine's auxiliary streams)."""
+        self._check_room(n)
         if self._dry:
             raise RuntimeError("dip-amd: a dry (host-memory) GroupedFits cannot launch anything")
         with torch.cuda.device(self.device):
             for _ in range(int(n)):
                 self._iteration()
-                self.iterations += 1
-                if self.monitor is not None:
-                    self.monitor.i += 1
+                self._issued(1)
 
     def capture(self, warmup=3):
         """`warmup` eager iterations (at least one), then the grouped iteration as ONE hipGraph (replayed by run()).  With a
@@ -651,13 +611,10 @@ class GroupedFits:
     def run(self, n=1):
         if self.graph is None:
             return self.step(n)
-        if self.monitor is not None:
-            self.monitor._check_room(n)
+        self._check_room(n)
         for _ in range(int(n)):
             self.graph.replay()
-        self.iterations += int(n)
-        if self.monitor is not None:
-            self.monitor.i += int(n)
+        self._issued(int(n))
 
     def step_counts(self):
         """Adam's step count of every instance, as the device holds it."""

@@ -21,7 +21,6 @@ with an SRHead and monitor=utils.fit_monitor.SRFitMonitor(...) the super-resolut
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import torch
@@ -421,7 +420,6 @@ class NativeIteration:
     def _check_monitor(self):
         """What can be said about `monitor` before the output size is known (the image shape: _build)."""
         from utils.fit_monitor import FitMonitor, SRFitMonitor
-        from utils.loss_head import SRHead
         m = self.monitor
         if m is None:
             return
@@ -429,12 +427,12 @@ class NativeIteration:
             raise TypeError("dip-amd: monitor must be a utils.fit_monitor.FitMonitor, an SRFitMonitor or None, got "
                             f"{type(m).__name__}")
         head = getattr(self, "head", None)
-        if isinstance(m, SRFitMonitor) and head is not None and not isinstance(head, SRHead):
+        if head is not None and m.head_kind not in (None, head.kind):
             raise TypeError(f"dip-amd: an SRFitMonitor records out_LR and out_HR of a utils.loss_head.SRHead, the head is a "
                             f"{type(head).__name__} (use a FitMonitor)")
         if m.dev != self.device:
             raise RuntimeError(f"dip-amd: the {type(m).__name__} lives on {m.dev}, the iteration runs on {self.device}")
-        if isinstance(m, FitMonitor) and m.engine is not None and m.engine is not self.engine:
+        if m.engine is not None and m.engine is not self.engine:
             raise ValueError("dip-amd: the FitMonitor back-tracks another net (it was built for a different skip() net)")
 
     # -------------------------------------------------------------------------------------------- the command arrays
@@ -464,14 +462,8 @@ class NativeIteration:
         out = self.out
         if out is None or tuple(out.shape) != (1, eng.n_out, eng.Hout, eng.Wout) or out.device != dev:
             out = torch.empty((1, eng.n_out, eng.Hout, eng.Wout), dtype=torch.float32, device=dev)
-        from utils.fit_monitor import SRFitMonitor
-        sr_mon = isinstance(m, SRFitMonitor)
-        if m is not None and not sr_mon and tuple(m.noisy.shape) != tuple(out.shape):
-            raise ValueError(f"dip-amd: the FitMonitor's image is {tuple(m.noisy.shape)}, the net output is {tuple(out.shape)}")
         loss0 = torch.zeros((), dtype=torch.float32, device=dev)
         desc = head._descriptor(eng, out, loss0)
-        if sr_mon:                                # (the head's LR buffer exists now: img_LR / img_HR against the two outputs)
-            m._check_outputs(out.shape, head.out_LR.shape, who="NativeIteration")
         pre = []
         if noisy:
             pre.append((lib.dip_noise_axpy_dev, (reg.saved.data_ptr(), reg.out.data_ptr(), reg.saved.numel(), reg.std,
@@ -497,14 +489,9 @@ class NativeIteration:
         if m is not None:
             # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the
             # parameters after this iteration's gradients were computed and before Adam applies them
-            mdesc = m._dev_descriptor(out, head.out_LR) if sr_mon else m._dev_descriptor(out)
+            # (the monitor checks its images against the outputs -- an SRHead's LR buffer exists now -- and says what it launches)
+            mdesc, mon = m._plan(eng, out, head)
             mdesc.loss = loss0.data_ptr()
-            mon = [(lib.dip_sr_monitor_dev, (C.byref(mdesc),), "sr_monitor_dev")] if sr_mon else \
-                [(lib.dip_fit_monitor_dev, (C.byref(mdesc),), "fit_monitor_dev")]
-            if not sr_mon and m.engine is not None:
-                snap = m._ensure_snapshot()
-                mon.append((lib.dip_arena_backtrack, (eng.params.data_ptr(), snap.data_ptr(), eng.params.numel(),
-                                                      m.state.data_ptr()), "arena_backtrack"))
             phases.insert(4, on_main(mon))
         lists = N.IterList(phases)
         views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]

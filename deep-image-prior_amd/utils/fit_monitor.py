@@ -67,6 +67,37 @@ import torch
 import dip_native as N
 
 
+_ptr = lambda t: None if t is None else t.data_ptr()
+
+
+# ---------------------------------------------------------------- the device-indexed records, said once
+# FitMonitor / SRFitMonitor (one fit, dip_optim.NativeIteration) and dip_group.GroupedFits (B fits through one launch list) fill
+# the descriptors and list the launches HERE; `m` carries the settings, the buffers are wherever the caller keeps them.
+def fit_monitor_descriptor(m, out, noisy, gt, out_avg, partial, records, counter, state, loss=None):
+    """DipFitMonitorDesc of monitor m (a FitMonitor or a GroupedFitMonitor) over these buffers."""
+    return N.DipFitMonitorDesc(_ptr(out), _ptr(noisy), _ptr(gt), _ptr(out_avg), noisy.numel(), m.exp_weight, m.backtrack_db,
+                               _ptr(loss), _ptr(partial), _ptr(records), m.capacity, m.show_every, 1 if m.backtracking else 0,
+                               0, _ptr(counter), _ptr(state))
+
+
+def fit_monitor_launches(lib, desc, params_ptr, n_arena, snapshot_ptr):
+    """dip_fit_monitor_dev and, with a snapshot arena, dip_arena_backtrack as (fn, args, name) triples."""
+    mon = [(lib.dip_fit_monitor_dev, (C.byref(desc),), "fit_monitor_dev")]
+    if snapshot_ptr is not None:
+        mon.append((lib.dip_arena_backtrack, (params_ptr, snapshot_ptr, n_arena, desc.state), "arena_backtrack"))
+    return mon
+
+
+def sr_monitor_descriptor(m, out_HR, out_LR, img_HR, img_LR, partial, records, counter, loss=None):
+    """DipSRMonitorDesc of monitor m (an SRFitMonitor or a GroupedSRFitMonitor) over these buffers."""
+    return N.DipSRMonitorDesc(_ptr(out_HR), _ptr(out_LR), _ptr(img_HR), _ptr(img_LR), out_HR.numel(), img_LR.numel(), _ptr(loss),
+                              _ptr(partial), _ptr(records), m.capacity, 0, _ptr(counter))
+
+
+def sr_monitor_launches(lib, desc):
+    return [(lib.dip_sr_monitor_dev, (C.byref(desc),), "sr_monitor_dev")]
+
+
 class _DeviceRecords:
     """What FitMonitor and SRFitMonitor share: a [capacity, len(COLUMNS)] record table in device memory, the host's count `i`
     of recorded iterations, and the device counter the *_dev kernels index the table with (NativeIteration(monitor=))."""
@@ -107,6 +138,8 @@ class _DeviceRecords:
 
 class FitMonitor(_DeviceRecords):
     COLUMNS = ("loss", "mse_noisy", "mse_gt", "mse_gt_sm", "psrn_noisy", "psrn_gt", "psrn_gt_sm", "fell_back")
+    head_kind = None                                                # any head: the record needs the net output only
+    backtracking = property(lambda self: self.engine is not None)
 
     def __init__(self, net, img_noisy, img_gt=None, exp_weight=0.99, show_every=100, backtrack_db=5.0,
                  backtracking=True, capacity=16384):
@@ -174,10 +207,16 @@ class FitMonitor(_DeviceRecords):
 
     def _dev_descriptor(self, out):
         """DipFitMonitorDesc over this monitor's buffers for the output buffer `out`; `loss` is filled in per iteration."""
-        ptr = lambda t: None if t is None else t.data_ptr()
-        return N.DipFitMonitorDesc(ptr(out), ptr(self.noisy), ptr(self.gt), ptr(self.out_avg), self.n, self.exp_weight,
-                                   self.backtrack_db, None, ptr(self.partial), ptr(self.records), self.capacity,
-                                   self.show_every, 1 if self.engine is not None else 0, 0, ptr(self.counter), ptr(self.state))
+        return fit_monitor_descriptor(self, out, self.noisy, self.gt, self.out_avg, self.partial, self.records, self.counter,
+                                      self.state)
+
+    def _plan(self, eng, out, head):
+        """(descriptor, launches) of an iteration that writes the net output to `out` (dip_optim.NativeIteration)."""
+        if tuple(self.noisy.shape) != tuple(out.shape):
+            raise ValueError(f"dip-amd: the FitMonitor's image is {tuple(self.noisy.shape)}, the net output is {tuple(out.shape)}")
+        desc = self._dev_descriptor(out)
+        return desc, fit_monitor_launches(self.lib, desc, eng.params.data_ptr(), eng.params.numel(),
+                                          _ptr(self._ensure_snapshot()))
 
     def _plan_key(self):
         """What a compiled command array (dip_optim.NativeIteration) was built from: buffers by identity, settings by value."""
@@ -198,6 +237,8 @@ class SRFitMonitor(_DeviceRecords):
     and no net: the reference closure has none of them.  update() is the eager form (dip_sr_monitor); NativeIteration(
     monitor=this) issues dip_sr_monitor_dev, which reads the row index from `counter`."""
     COLUMNS = ("loss", "mse_LR", "mse_HR", "psnr_LR", "psnr_HR")
+    head_kind = "sr"                                                # the record needs the two outputs of an SRHead
+    engine = None                                                   # no back-tracking: tied to no net
 
     def __init__(self, img_LR, img_HR=None, capacity=16384):
         if not isinstance(img_LR, torch.Tensor) or not img_LR.is_cuda or (img_HR is not None and not img_HR.is_cuda):
@@ -253,10 +294,14 @@ class SRFitMonitor(_DeviceRecords):
 
     def _dev_descriptor(self, out_HR, out_LR):
         """DipSRMonitorDesc over this monitor's buffers for the output buffers; `loss` is filled in per iteration."""
-        ptr = lambda t: None if t is None else t.data_ptr()
-        return N.DipSRMonitorDesc(ptr(out_HR), ptr(out_LR), ptr(self.img_HR), ptr(self.img_LR), out_HR.numel(), self.n_lr,
-                                  None, ptr(self._ensure_partial(out_HR.numel())), ptr(self.records), self.capacity, 0,
-                                  ptr(self.counter))
+        return sr_monitor_descriptor(self, out_HR, out_LR, self.img_HR, self.img_LR, self._ensure_partial(out_HR.numel()),
+                                     self.records, self.counter)
+
+    def _plan(self, eng, out, head):
+        """(descriptor, launches) of an iteration under `head` (an SRHead whose LR buffer exists) that writes out_HR to `out`."""
+        self._check_outputs(out.shape, head.out_LR.shape, who="NativeIteration")
+        desc = self._dev_descriptor(out, head.out_LR)
+        return desc, sr_monitor_launches(self.lib, desc)
 
     def _plan_key(self):
         return (id(self), id(self.records), id(self.partial), id(self.counter), id(self.img_LR), id(self.img_HR), self.capacity)
@@ -277,6 +322,11 @@ class _GroupedRecords:
         self._group = None         # weak: the group holds the monitor, and a cycle would keep slab and hipGraph alive
         self._adopted = False
         self.records = self.counter = None
+
+    def _adopt(self, group, **views):
+        """`group` takes this monitor: the [B, ...] views over its slab rows become attributes."""
+        self._group, self._adopted = weakref.ref(group), True
+        self.__dict__.update(views)
 
     def _check_images(self, imgs, shapes, name, what):
         """`imgs` (None, or one [1,C,H,W] image per instance) against the shapes the group works on."""
@@ -336,10 +386,6 @@ class GroupedFitMonitor(_GroupedRecords):
         """imgs_gt against the group's targets: one [1,C,H,W] image per instance, shaped like the target."""
         self._check_images(self.imgs_gt, [t.shape for t in targets], "imgs_gt", "the target")
 
-    def _adopt(self, group, records, state, counter, out_avg, snapshot):
-        self._group, self._adopted = weakref.ref(group), True
-        self.records, self.state, self.counter, self.out_avg, self.snapshot = records, state, counter, out_avg, snapshot
-
 
 class GroupedSRFitMonitor(_GroupedRecords):
     """SRFitMonitor for the B fits of a dip_group.GroupedFits(downsamplers=...): settings only.  The group that adopts it
@@ -364,7 +410,3 @@ class GroupedSRFitMonitor(_GroupedRecords):
     def _check_hr(self, B, hr_shape):
         """imgs_HR against the planned net output: one [1,C,H,W] image per instance."""
         self._check_images(self.imgs_HR, [hr_shape] * B, "imgs_HR", "the net output")
-
-    def _adopt(self, group, records, counter):
-        self._group, self._adopted = weakref.ref(group), True
-        self.records, self.counter = records, counter

@@ -42,6 +42,8 @@ tv_beta < 1 a pixel whose right and lower neighbours equal it gives NaN gradient
 
 Both heads describe their launches ONCE, as the (fn, args, name) triples SkipEngine.forward / backward issue one by one and
 dip_optim.NativeIteration compiles into its command arrays: `with_out_conv`, `_descriptor`, `fwd_launches`, `bwd_launches`.
+The descriptors and the triples themselves are module-level functions (mse_* / sr_*), which dip_group.GroupedFits calls with
+the buffers of its slab.
 """
 import ctypes as C
 
@@ -50,86 +52,30 @@ import torch
 import dip_native as N
 
 
-class MSEHead:
-    kind = "mse"
-    with_out_conv = False       # dip_loss_head_fwd runs the output conv itself: the forward list stops in front of it
-
-    def __init__(self, net, target, mask=None):
-        eng = getattr(net, "__dict__", {}).get("_dip_engine")
-        if eng is None or isinstance(eng, Exception):
-            raise RuntimeError("dip-amd: MSEHead needs a net built by models.skip.skip()")
-        if not target.is_cuda:
-            raise RuntimeError("dip-amd: MSEHead works on MI355X tensors only (no CPU fallback)")
-        self.net, self.engine = net, eng
-        oc = eng.out_conv
-        if oc.ks != 1 or oc.Cout > 4:
-            raise NotImplementedError("dip-amd: the fused loss head covers a 1x1 output conv with <= 4 channels "
-                                      "(n_channels 1 or 3 in every reference notebook)")
-        if target.dim() != 4 or target.shape[0] != 1 or target.shape[1] != oc.Cout:
-            raise ValueError(f"MSEHead: target must be [1,{oc.Cout},H,W], got {tuple(target.shape)}")
-        self.target = target.detach().contiguous().float()
-        self.mask = None
-        self.mask_c = 0
-        if mask is not None:
-            m = mask.detach().to(target.device).float()
-            while m.dim() < 4:
-                m = m[None]
-            if m.shape[0] != 1 or m.shape[1] not in (1, oc.Cout) or m.shape[2:] != target.shape[2:]:
-                raise ValueError(f"MSEHead: mask must be [1,1|{oc.Cout},H,W], got {tuple(m.shape)}")
-            self.mask, self.mask_c = m.contiguous(), int(m.shape[1])
-        self._scratch = None
-
-    def _descriptor(self, eng, out, loss):
-        """DipLossHeadDesc for the engine's current plan (called by SkipEngine.forward)."""
-        H, W = eng.Hout, eng.Wout
-        if tuple(self.target.shape[2:]) != (H, W):
-            raise ValueError(f"MSEHead: target is {tuple(self.target.shape[2:])}, the net output is {(H, W)}")
-        a = eng.last_act
-        oc = eng.out_conv
-        nblk = eng.lib.dip_loss_head_nblk(H * W, oc.Cin)
-        dev = out.device
-        if self._scratch is None or self._scratch.numel() != nblk or self._scratch.device != dev:
-            self._scratch = torch.empty(nblk, dtype=torch.float32, device=dev)
-        partials = self._scratch
-        tr = a.transform()
-        self._keep = (out.detach(), tr)     # (not `loss`: it becomes the autograd output and would pin the graph)
-        ptr = lambda t, off=0: None if t is None else t.data_ptr() + 4 * off
-        return N.DipLossHeadDesc(ptr(a.buf), a.Cs, oc.Cin, tr, ptr(eng.params, oc.w_off),
-                                 ptr(eng.params, oc.b_off) if oc.b_off >= 0 else None, oc.Cout, H * W,
-                                 1 if eng.need_sigmoid else 0, ptr(self.target), ptr(self.mask), self.mask_c,
-                                 ptr(out), ptr(partials), nblk, ptr(loss))
-
-    def fwd_launches(self, eng, desc):
-        """The head's forward as (fn, args, name) triples; args without the trailing stream."""
-        return [(eng.lib.dip_loss_head_fwd, (C.byref(desc),), "loss_head_fwd")]
-
-    def bwd_launches(self, eng, desc, gscale_ptr):
-        """What writes eng.dy_out (the gradient wrt the output conv's result) from d loss at gscale_ptr."""
-        return [(eng.lib.dip_loss_head_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
-                 "loss_head_bwd")]
-
-    def _check_state(self):
-        pass
-
-    def _plan_key(self):
-        """What a compiled command array (dip_optim.NativeIteration) was built from, objects by identity."""
-        return (self.kind, id(self.target), self.target.data_ptr(), id(self.mask), self.mask_c)
-
-    def _plan_keep(self):
-        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
-        return (self.target, self.mask, self._keep, self._scratch)
-
-    def __call__(self, net_input):
-        import dip_engine
-        if not self.net.training:
-            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented")
-        loss, out = dip_engine.run_net_loss(self.engine, self, net_input)
-        return loss, out
+# ---------------------------------------------------------------- the two tails, said once
+# MSEHead / SRHead (one fit) and dip_group.GroupedFits (B fits through one launch list) fill the descriptors and list the
+# launches HERE; they differ only in where the buffers live.
+def mse_descriptor(eng, target_ptr, mask_ptr, mask_c, out_ptr, partials_ptr, nblk, loss_ptr):
+    """(DipLossHeadDesc for the engine's current plan, the DipTransform it points into: the caller keeps that alive)."""
+    a, oc = eng.last_act, eng.out_conv
+    tr = a.transform()
+    p = eng.params.data_ptr()
+    return N.DipLossHeadDesc(a.buf.data_ptr(), a.Cs, oc.Cin, tr, p + 4 * oc.w_off, p + 4 * oc.b_off if oc.b_off >= 0 else None,
+                             oc.Cout, eng.Hout * eng.Wout, 1 if eng.need_sigmoid else 0, target_ptr, mask_ptr, mask_c,
+                             out_ptr, partials_ptr, nblk, loss_ptr), tr
 
 
-# ---------------------------------------------------------------- the super-resolution tail, said once
-# SRHead (one fit) and dip_group.GroupedFits(downsamplers=) (B fits through one launch list) check the down-sampler, derive the
-# geometry, fill DipSRLossDesc and list the launches HERE; they differ only in where the buffers live.
+def mse_fwd_launches(eng, desc):
+    """The head's forward as (fn, args, name) triples; args without the trailing stream."""
+    return [(eng.lib.dip_loss_head_fwd, (C.byref(desc),), "loss_head_fwd")]
+
+
+def mse_bwd_launches(eng, desc, gscale_ptr):
+    """What writes eng.dy_out (the gradient wrt the output conv's result) from d loss at gscale_ptr."""
+    return [(eng.lib.dip_loss_head_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
+             "loss_head_bwd")]
+
+
 def sr_check_fixed_taps(d, who="SRHead"):
     """The fused tail applies the FIXED taps: a down-sampler that is (or may be) trained is refused."""
     if getattr(d, "_dense", False) or getattr(d, "_nondiag", False) or d.downsampler_.weight.requires_grad \
@@ -172,35 +118,88 @@ def sr_check_tv(tv_weight, tv_beta, who="SRHead"):
     return w, beta
 
 
-def sr_tv_descriptor(eng, sr_desc, tv_weight_ptr, tv_partials_ptr, tv_nblk, beta):
+def sr_tv_descriptor(sr_desc, tv_weight_ptr, tv_partials_ptr, tv_nblk, beta):
     """DipSRTVDesc: the DipSRLossDesc of the same fit + the TV term's device scalar, partials and beta."""
     return N.DipSRTVDesc(sr_desc, tv_weight_ptr, tv_partials_ptr, tv_nblk, beta)
 
 
-def sr_tv_fwd_launches(eng, desc):
-    """dip_head_fwd + dip_sr_tv_loss_fwd: total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR, beta)."""
-    Cs = N.round_up(eng.n_out, 4)
-    return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.sr.out, eng.n_out, eng.Hout * eng.Wout, Cs,
-                                    1 if eng.need_sigmoid else 0), "head_fwd"),
-            (eng.lib.dip_sr_tv_loss_fwd, (C.byref(desc),), "sr_tv_loss_fwd")]
-
-
-def sr_tv_bwd_launches(eng, desc, gscale_ptr):
-    return [(eng.lib.dip_sr_tv_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
-             "sr_tv_loss_bwd")]
-
-
 def sr_fwd_launches(eng, desc):
-    """dip_head_fwd (NHWC -> NCHW + sigmoid: out_HR as net(x) writes it) + dip_sr_loss_fwd, as (fn, args, name) triples."""
-    Cs = N.round_up(eng.n_out, 4)
-    return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.out, eng.n_out, eng.Hout * eng.Wout, Cs,
+    """dip_head_fwd (NHWC -> NCHW + sigmoid: out_HR as net(x) writes it) + dip_sr_loss_fwd, as (fn, args, name) triples; for
+    a DipSRTVDesc dip_sr_tv_loss_fwd: total_loss = mse(out_LR, img_LR) + tv_weight * tv_loss(out_HR, beta)."""
+    fn, name = (eng.lib.dip_sr_tv_loss_fwd, "sr_tv_loss_fwd") if isinstance(desc, N.DipSRTVDesc) else \
+        (eng.lib.dip_sr_loss_fwd, "sr_loss_fwd")
+    return [(eng.lib.dip_head_fwd, (eng.y_out.data_ptr(), desc.out, eng.n_out, eng.Hout * eng.Wout, N.round_up(eng.n_out, 4),
                                     1 if eng.need_sigmoid else 0), "head_fwd"),
-            (eng.lib.dip_sr_loss_fwd, (C.byref(desc),), "sr_loss_fwd")]
+            (fn, (C.byref(desc),), name)]
 
 
 def sr_bwd_launches(eng, desc, gscale_ptr):
-    return [(eng.lib.dip_sr_loss_bwd, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)),
-             "sr_loss_bwd")]
+    fn, name = (eng.lib.dip_sr_tv_loss_bwd, "sr_tv_loss_bwd") if isinstance(desc, N.DipSRTVDesc) else \
+        (eng.lib.dip_sr_loss_bwd, "sr_loss_bwd")
+    return [(fn, (C.byref(desc), gscale_ptr, eng.dy_out.data_ptr(), N.round_up(eng.n_out, 4)), name)]
+
+
+class MSEHead:
+    kind = "mse"
+    with_out_conv = False       # dip_loss_head_fwd runs the output conv itself: the forward list stops in front of it
+    fwd_launches, bwd_launches = staticmethod(mse_fwd_launches), staticmethod(mse_bwd_launches)
+
+    def __init__(self, net, target, mask=None):
+        eng = getattr(net, "__dict__", {}).get("_dip_engine")
+        if eng is None or isinstance(eng, Exception):
+            raise RuntimeError("dip-amd: MSEHead needs a net built by models.skip.skip()")
+        if not target.is_cuda:
+            raise RuntimeError("dip-amd: MSEHead works on MI355X tensors only (no CPU fallback)")
+        self.net, self.engine = net, eng
+        oc = eng.out_conv
+        if oc.ks != 1 or oc.Cout > 4:
+            raise NotImplementedError("dip-amd: the fused loss head covers a 1x1 output conv with <= 4 channels "
+                                      "(n_channels 1 or 3 in every reference notebook)")
+        if target.dim() != 4 or target.shape[0] != 1 or target.shape[1] != oc.Cout:
+            raise ValueError(f"MSEHead: target must be [1,{oc.Cout},H,W], got {tuple(target.shape)}")
+        self.target = target.detach().contiguous().float()
+        self.mask = None
+        self.mask_c = 0
+        if mask is not None:
+            m = mask.detach().to(target.device).float()
+            while m.dim() < 4:
+                m = m[None]
+            if m.shape[0] != 1 or m.shape[1] not in (1, oc.Cout) or m.shape[2:] != target.shape[2:]:
+                raise ValueError(f"MSEHead: mask must be [1,1|{oc.Cout},H,W], got {tuple(m.shape)}")
+            self.mask, self.mask_c = m.contiguous(), int(m.shape[1])
+        self._scratch = None
+
+    def _descriptor(self, eng, out, loss):
+        """DipLossHeadDesc for the engine's current plan (called by SkipEngine.forward)."""
+        H, W = eng.Hout, eng.Wout
+        if tuple(self.target.shape[2:]) != (H, W):
+            raise ValueError(f"MSEHead: target is {tuple(self.target.shape[2:])}, the net output is {(H, W)}")
+        nblk = eng.lib.dip_loss_head_nblk(H * W, eng.out_conv.Cin)
+        dev = out.device
+        if self._scratch is None or self._scratch.numel() != nblk or self._scratch.device != dev:
+            self._scratch = torch.empty(nblk, dtype=torch.float32, device=dev)
+        desc, tr = mse_descriptor(eng, self.target.data_ptr(), None if self.mask is None else self.mask.data_ptr(), self.mask_c,
+                                  out.data_ptr(), self._scratch.data_ptr(), nblk, loss.data_ptr())
+        self._keep = (out.detach(), tr)     # (not `loss`: it becomes the autograd output and would pin the graph)
+        return desc
+
+    def _check_state(self):
+        pass
+
+    def _plan_key(self):
+        """What a compiled command array (dip_optim.NativeIteration) was built from, objects by identity."""
+        return (self.kind, id(self.target), self.target.data_ptr(), id(self.mask), self.mask_c)
+
+    def _plan_keep(self):
+        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
+        return (self.target, self.mask, self._keep, self._scratch)
+
+    def __call__(self, net_input):
+        import dip_engine
+        if not self.net.training:
+            raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented")
+        loss, out = dip_engine.run_net_loss(self.engine, self, net_input)
+        return loss, out
 
 
 class SRHead:
@@ -210,6 +209,7 @@ class SRHead:
     weight lives in a device scalar, rewritten by set_tv_weight() without a re-plan."""
     kind = "sr"
     with_out_conv = True        # the forward list runs to its end; dip_head_fwd writes out_HR as net(x) does
+    fwd_launches, bwd_launches = staticmethod(sr_fwd_launches), staticmethod(sr_bwd_launches)
 
     def __init__(self, net, img_LR, downsampler, tv_weight=0.0, tv_beta=0.5):
         self.tv_weight, self.tv_beta = sr_check_tv(tv_weight, tv_beta)
@@ -278,7 +278,7 @@ class SRHead:
             self._tv_scratch = torch.empty(tv_nblk, dtype=torch.float32, device=dev)
         if self._tvw is None or self._tvw.device != dev:
             self._tvw = torch.full((1,), self.tv_weight, dtype=torch.float32, device=dev)
-        return sr_tv_descriptor(eng, sr, self._tvw.data_ptr(), self._tv_scratch.data_ptr(), tv_nblk, self.tv_beta)
+        return sr_tv_descriptor(sr, self._tvw.data_ptr(), self._tv_scratch.data_ptr(), tv_nblk, self.tv_beta)
 
     def set_tv_weight(self, w):
         """Another tv_weight > 0 for the calls that follow: the device scalar is rewritten in stream order, nothing is
@@ -290,12 +290,6 @@ class SRHead:
         self.tv_weight = w
         if self._tvw is not None:
             self._tvw.fill_(w)
-
-    def fwd_launches(self, eng, desc):
-        return sr_tv_fwd_launches(eng, desc) if self._tv else sr_fwd_launches(eng, desc)
-
-    def bwd_launches(self, eng, desc, gscale_ptr):
-        return sr_tv_bwd_launches(eng, desc, gscale_ptr) if self._tv else sr_bwd_launches(eng, desc, gscale_ptr)
 
     def _plan_key(self):
         d = self.downsampler
