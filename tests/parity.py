@@ -54,8 +54,10 @@ def zero_grad_keys(spec, sd=None):
         initialisation) and whose output reaches, through LeakyReLU (positively homogeneous) and
         up-sampling / concatenation only, a PER-CHANNEL BatchNorm -- the skip-branch BatchNorm, the last
         BatchNorm of every scale below the top, and the deepest down_b BatchNorm: scaling one of their
-        channels is undone by the concat BatchNorm, so d loss / d gamma_c == 0 for every channel."""
+        channels is undone by the concat BatchNorm, so d loss / d gamma_c == 0 for every channel.  Swish and ELU are not
+        positively homogeneous: with them these gammas carry a real gradient and take the relative bound."""
     keys, _ = O.scale_keys(spec)
+    homogeneous = getattr(spec, "act_fun", "LeakyReLU") not in ("Swish", "ELU")
     out = set()
     n = spec.n_scales
     for i, k in enumerate(keys):
@@ -70,7 +72,7 @@ def zero_grad_keys(spec, sd=None):
         # produces (with zero padding the border breaks this, so only for pad == 'reflection')
         if spec.pad == "reflection":
             out.add(k.cat_bn + ".bias")
-        if sd is not None:
+        if sd is not None and homogeneous:
             cands = [k.skip_bn] if k.skip_bn else []
             if i >= 1:
                 cands.append(k.up1_bn if k.up1_bn else k.up_bn)

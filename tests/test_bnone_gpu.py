@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 import dip_native as N  # noqa: E402
 from dip_native import round_up  # noqa: E402
 import hipops as H  # noqa: E402
-from test_kernels_gpu import _check  # noqa: E402
+from test_kernels_gpu import _act, _bn_off_the_kink, _check  # noqa: E402
 
 
 def _state(y, gamma, beta):
@@ -48,12 +48,14 @@ def test_bn_bwd_one_matches_autograd(dev, Cc, Hh, Ww, P, slope):
     gamma = torch.rand(Cc, generator=g) + 0.5
     beta = torch.randn(Cc, generator=g)
     G = torch.randn(1, Cc, Hh + 2 * P, Ww + 2 * P, generator=g)
+    if slope == -3.0:
+        y = _bn_off_the_kink(y, gamma, beta)
 
     def ref(dt):
         yy = y.to(dt).requires_grad_(True)
         ga, be = gamma.to(dt).requires_grad_(True), beta.to(dt).requires_grad_(True)
         u = F.batch_norm(yy, None, None, ga, be, True, 0.1, 1e-5)
-        u = torch.maximum(u, slope * u)
+        u = _act(u, slope)
         if P:
             u = F.pad(u, (P,) * 4, mode="reflect")
         (u * G.to(dt)).sum().backward()
@@ -138,7 +140,7 @@ def test_bn_bwd_one_crop_window(dev):
     (0, 8, 30, 47, "bilinear", (1, 0)),         # centre crop with an offset (a skip-less scale at a non-divisible size)
     (4, 128, 128, 128, "bilinear", (0, 0)),     # 64 x 64 deep branch: 4 pixels per thread, 16 loads each
 ])
-def test_upsample_bwd_one_matches_autograd(dev, ns, nd, Hh, Ww, mode, od):
+def test_upsample_bwd_one_matches_autograd(dev, ns, nd, Hh, Ww, mode, od, slope=0.2):
     lib = N.lib()
     g = torch.Generator().manual_seed(5)
     ody, odx = od
@@ -146,13 +148,14 @@ def test_upsample_bwd_one_matches_autograd(dev, ns, nd, Hh, Ww, mode, od):
     d = torch.randn(1, nd, Hl, Wl, generator=g) * 1.5 + torch.randn(1, nd, 1, 1, generator=g)
     gamma, beta = torch.rand(nd, generator=g) + 0.5, torch.randn(nd, generator=g) * 0.3
     Gc = torch.randn(1, ns + nd, Hh, Ww, generator=g)
-    slope = 0.2
+    if slope == -3.0:
+        d = _bn_off_the_kink(d, gamma, beta)
 
     def ref(dt):
         dd = d.to(dt).requires_grad_(True)
         ga, be = gamma.to(dt).requires_grad_(True), beta.to(dt).requires_grad_(True)
         u = F.batch_norm(dd, None, None, ga, be, True, 0.1, 1e-5)
-        u = torch.maximum(u, slope * u)
+        u = _act(u, slope)
         up = F.interpolate(u, scale_factor=2, mode=mode)[:, :, ody:ody + Hh, odx:odx + Ww]
         (up * Gc[:, ns:].to(dt)).sum().backward()
         return dd.grad, ga.grad, be.grad
@@ -196,12 +199,14 @@ def test_bn_bwd_finalise_in_the_apply_prologue(dev, Cc, Hh, Ww, P, slope):
     y = torch.randn(1, Cc, Hh, Ww, generator=g) * 2.0 + torch.randn(1, Cc, 1, 1, generator=g) * 3.0
     gamma, beta = torch.rand(Cc, generator=g) + 0.5, torch.randn(Cc, generator=g)
     G = torch.randn(1, Cc, Hh + 2 * P, Ww + 2 * P, generator=g)
+    if slope == -3.0:
+        y = _bn_off_the_kink(y, gamma, beta)
 
     def ref(dt):
         yy = y.to(dt).requires_grad_(True)
         ga, be = gamma.to(dt).requires_grad_(True), beta.to(dt).requires_grad_(True)
         u = F.batch_norm(yy, None, None, ga, be, True, 0.1, 1e-5)
-        u = torch.maximum(u, slope * u)
+        u = _act(u, slope)
         if P:
             u = F.pad(u, (P,) * 4, mode="reflect")
         (u * G.to(dt)).sum().backward()

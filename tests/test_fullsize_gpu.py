@@ -83,6 +83,28 @@ def test_default_net_iter1_vs_oracle(dev, size):
            f"default net {size}x{size}")
 
 
+@pytest.mark.parametrize("act", ["Swish", "ELU"])
+def test_default_net_128_act_vs_oracle(dev, act):
+    """The default skip-net with act_fun = 'Swish' / 'ELU' (models/common.py:76-92 of the reference) at 128x128: the top
+    scale on the bf16 pipe (64-column form, TR == 2), the lower scales on the register-staged and small-layer kernels, every
+    BatchNorm backward with the code's derivative -- the engine's own routing of coded layers, end to end, under the
+    thresholds of the LeakyReLU cases.  (ReLU stays at kernel level, tests/test_act_codes_gpu.py, and in tiny_relu: the
+    oracle imposes a branch pattern for LeakyReLU only.)"""
+    import dataclasses
+    from models import get_net
+    from utils.common_utils import get_noise
+    torch.manual_seed(0)
+    net = get_net(32, "skip", "reflection", act_fun=act, skip_n33d=128, skip_n33u=128, skip_n11=4, num_scales=5,
+                  upsample_mode="bilinear")
+    spec = dataclasses.replace(O.default_spec(), act_fun=act)
+    z = get_noise(32, "noise", (128, 128))
+    np.random.seed(0)
+    target = torch.from_numpy(np.random.rand(1, 3, 128, 128).astype(np.float32))
+    tg = target.to(dev)
+    _iter1(dev, net, spec, z, lambda o, dt: F.mse_loss(o, target.to(dt)), lambda o: F.mse_loss(o, tg),
+           f"default net 128x128 {act}")
+
+
 def test_sr_closure_512_vs_oracle(dev):
     """BASELINE configs[2]: default net at 512x512, loss through Downsampler(3, 4, 'lanczos2',
     phase=0.5, preserve_size=True) against a 128x128 LR image."""

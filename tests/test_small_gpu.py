@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 import dip_native as N  # noqa: E402
 from dip_native import round_up  # noqa: E402
 import hipops as H  # noqa: E402
-from test_kernels_gpu import _apply_tr, _check, _mk, _ref_conv, REFLECT, ZERO, REPLICATE  # noqa: E402
+from test_kernels_gpu import _act_grad, _apply_tr, _bn_off_the_kink, _check, _mk, _ref_conv, REFLECT, ZERO, REPLICATE  # noqa: E402
 
 SMALL_CASES = [
     # Cin, Cout, ks, stride, pad, H, W, transform  -- the low-resolution layers of the notebooks' nets + ragged shapes
@@ -45,10 +45,9 @@ SMALL_CASES = [
 
 
 @pytest.mark.parametrize("case", SMALL_CASES, ids=lambda c: "x".join(map(str, c)))
-def test_conv_small_forward_and_stats(dev, case):
+def test_conv_small_forward_and_stats(dev, case, slope=0.2):
     Cin, Cout, ks, stride, pad, Hh, Ww, use_tr = case
     x, w, b, a, bb = _mk(case)
-    slope = 0.2
     ref64 = _ref_conv(_apply_tr(x, a, bb, slope, torch.float64), w, b, stride, pad, torch.float64)
     ref32 = _ref_conv(_apply_tr(x, a, bb, slope, torch.float32), w, b, stride, pad, torch.float32)
     tr = (a.to(dev), bb.to(dev), slope) if use_tr else (None, None, 1.0)
@@ -126,7 +125,7 @@ def test_conv_small_dgrad(dev, case):
 
 
 @pytest.mark.parametrize("case", [c for c in DGRAD_CASES if c[4] != REPLICATE], ids=lambda c: "x".join(map(str, c)))
-def test_conv_small_dgrad_with_fused_batchnorm_backward(dev, case):
+def test_conv_small_dgrad_with_fused_batchnorm_backward(dev, case, slope=0.2):
     """Phases 1 and 2 of the backward of the BatchNorm + LeakyReLU that produced the conv's input, inside the data-gradient
     launch: dgamma, dbeta, k1 = sum(dz) / N, k2 = sum(dz * xhat) / N with dz = g * lrelu'(a y + b), against autograd."""
     Cin, Cout, ks, stride, pad, Hh, Ww = case
@@ -135,7 +134,8 @@ def test_conv_small_dgrad_with_fused_batchnorm_backward(dev, case):
     yraw = torch.randn(1, Cin, Hh, Ww, generator=g0)              # raw output of the producer conv
     gamma = torch.rand(Cin, generator=g0) + 0.5
     beta = torch.randn(Cin, generator=g0) * 0.3
-    slope = 0.2
+    if slope == -3.0:
+        yraw = _bn_off_the_kink(yraw, gamma, beta)
     out = {}
     for dt in (torch.float64, torch.float32):
         yy = yraw.to(dt)
@@ -145,7 +145,7 @@ def test_conv_small_dgrad_with_fused_batchnorm_backward(dev, case):
         bcoef = beta.to(dt) - mu * a
         z = yy * a.view(1, -1, 1, 1) + bcoef.view(1, -1, 1, 1)
         gfold = res[dt]
-        dz = gfold * torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+        dz = gfold * _act_grad(z, slope)
         xh = (yy - mu.view(1, -1, 1, 1)) * rstd.view(1, -1, 1, 1)
         out[dt] = dict(s1=dz.sum((0, 2, 3)), s2=(dz * xh).sum((0, 2, 3)), state=torch.stack([mu, rstd, a, bcoef]))
     Cs = round_up(Cin, 4)
@@ -159,7 +159,7 @@ def test_conv_small_dgrad_with_fused_batchnorm_backward(dev, case):
     yy = yraw.double()
     st = state[:, :Cin].double()
     z = yy * st[2].view(1, -1, 1, 1) + st[3].view(1, -1, 1, 1)
-    dz = res[torch.float64] * torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+    dz = res[torch.float64] * _act_grad(z, slope)
     xh = (yy - st[0].view(1, -1, 1, 1)) * st[1].view(1, -1, 1, 1)
     s1, s2 = dz.sum((0, 2, 3)), (dz * xh).sum((0, 2, 3))
     scale = float(dz.abs().sum((0, 2, 3)).max())              # sums of npix terms of mixed sign: bound relative to sum |dz|
