@@ -309,8 +309,9 @@ class SkipEngine:
             off += r.fwd_elems
             r.dgrad_off = off
             off += r.dgrad_elems
-            recs[k] = N.DipPackRec(r.w_off, r.fwd_off, r.dgrad_off, r.Cout, r.Cin, r.ks, round_up(r.Cin, 4),
-                                   round_up(r.Cout, 32), round_up(r.Cout, 4), round_up(r.Cin, 32))
+            recs[k] = N.DipPackRec(w_off=r.w_off, fwd_off=r.fwd_off, dgrad_off=r.dgrad_off, Cout=r.Cout, Cin=r.Cin, KS=r.ks,
+                                   CinP4=round_up(r.Cin, 4), CoutP32=round_up(r.Cout, 32), CoutP4=round_up(r.Cout, 4),
+                                   CinP32=round_up(r.Cin, 32))
             max_elems = max(max_elems, r.fwd_elems + r.dgrad_elems)
         self.packed = self._dalloc(off, zero=True)
         # three-bf16-plane copies of the 3x3 stride-1 weights (bf16-pipe convolution), when the library has it switched on
@@ -333,7 +334,8 @@ class SkipEngine:
                     r.dgrad3_off = off3
                     off3 += kk * nchD * 3 * CinP * 16
                     max3 = max(max3, kk * 16 * (nchF * CoutP + nchD * CinP))
-                recs3[k] = N.DipPackRec3(r.w_off, r.fwd3_off, r.dgrad3_off, r.Cout, r.Cin, r.ks, nchF, CoutP, nchD, CinP)
+                recs3[k] = N.DipPackRec3(w_off=r.w_off, fwd_off=r.fwd3_off, dgrad_off=r.dgrad3_off, Cout=r.Cout, Cin=r.Cin,
+                                         KS=r.ks, nchF=nchF, CoutP32=CoutP, nchD=nchD, CinP32=CinP)
             self.packed3 = self._dalloc(max(off3, 8), torch.int16, zero=True)
             self.pack_recs3 = self._dcopy(bytes(recs3))
             self.pack_max3 = max3
@@ -356,35 +358,54 @@ class SkipEngine:
         self._alloc.append(t)          # the launch descriptors hold raw pointers: keep every buffer alive
         return t
 
+    # The shared scratch buffers (float32), in allocation order: BatchNorm partials of the forward convs, partial sums of the
+    # BatchNorm backward, weight- / bias-gradient slabs, those of the second bulk stream, split-K workspace; stats2 / ws2 /
+    # bwd2 serve the skip branch (side stream); bwd3 holds the fused BatchNorm-backward partials of the thin data-gradient
+    # columns.  "tickets" (int32, allocated last) are the arrival counters of the in-launch finalisations (bn_ticket.h).
+    _SCRATCH = ("stats", "bwd", "wg", "wgb", "wg2", "wgb2", "ws", "stats2", "ws2", "bwd2", "bwd3")
+
     def _reset_sizing(self):
         """Sizes of the shared scratch buffers, accumulated by the sizing pass of the planner."""
-        self.stat_need = self.wg_need = self.wgb_need = self.bwdp_need = self.ws_need = 4
-        self.wg2_need = self.wgb2_need = 4             # slab scratch of the second bulk stream
-        self.stat2_need = self.ws2_need = 4            # scratch of the skip-branch convs (side stream)
-        self.bwdp2_need = 4                            # ... and of the skip-branch BatchNorm backward
-        self.bwdp3_need = 4                            # fused BatchNorm-backward partials of the thin data-gradient columns
-        self.ticket_need = 8                           # arrival counters of the in-launch finalisations (bn_ticket.h)
+        self._need = dict.fromkeys(self._SCRATCH, 4)
+        self._need["tickets"] = 8
 
-    def _build_plan(self, H, W, Cin_img):
-        if min(H, W) < 2 ** self.nscales:
-            raise NotImplementedError(f"dip-amd: input {H}x{W} is too small for {self.nscales} scales")
+    def _scratch(self, name, n):
+        """The shared scratch buffer `name`, of which the caller uses n elements.  Sizing pass: records the largest n and
+        returns None; emitting pass: the buffer, which the sizing pass must have measured at least that large."""
+        if self._sizing:
+            self._need[name] = max(self._need[name], n)
+            return None
+        assert n <= self._need[name], (name, n, self._need[name])
+        return self._pool[name]
+
+    def _has_big_layer(self, H, W) -> bool:
+        """Is a conv of the net a big MFMA-bound layer at this input size (see bulk2_max_pixels in _init_common)?"""
+        h, w = H, W
+        for sc in self.sc:
+            hl, wl = ((h + 1) // 2, (w + 1) // 2) if sc.pool is None else (h // 2, w // 2)
+            for r, px in ((sc.down_a, hl * wl), (sc.down_b, hl * wl), (sc.up, h * w), (sc.up1, h * w)):
+                if r is not None and r.ks >= 3 and r.Cin >= 96 and r.Cout >= 96 and px >= 65536:
+                    return True
+            h, w = hl, wl
+        return False
+
+    def _begin_plan(self, H, W, Cin_img):
+        """What the plan of every backbone starts with: the shape, no compiled lists, no buffers, scratch sizes reset, and
+        the second bulk stream iff the net has no big layer at this input size (unless DIP_BULK2_MAX_PIXELS decided)."""
         self.H, self.W, self.Cimg = H, W, Cin_img
         self._clists = {}
         self._reset_sizing()
         self._alloc = []
-        oc = self.out_conv
-        self.n_out = oc.Cout
+        self.n_out = self.out_conv.Cout
         if getattr(self, "_bulk2_auto", self.bulk2_max_pixels < 0):
-            # second bulk stream iff no conv of the net is a big MFMA-bound layer at this input size (see __init__)
             self._bulk2_auto = True
-            big, h, w = False, H, W
-            for sc in self.sc:
-                hl, wl = ((h + 1) // 2, (w + 1) // 2) if sc.pool is None else (h // 2, w // 2)
-                for r, px in ((sc.down_a, hl * wl), (sc.down_b, hl * wl), (sc.up, h * w), (sc.up1, h * w)):
-                    if r is not None and r.ks >= 3 and r.Cin >= 96 and r.Cout >= 96 and px >= 65536:
-                        big = True
-                h, w = hl, wl
-            self.bulk2_max_pixels = 0 if big else 100000
+            self.bulk2_max_pixels = 0 if self._has_big_layer(H, W) else 100000
+
+    def _build_plan(self, H, W, Cin_img):
+        if min(H, W) < 2 ** self.nscales:
+            raise NotImplementedError(f"dip-amd: input {H}x{W} is too small for {self.nscales} scales")
+        self._begin_plan(H, W, Cin_img)
+        oc = self.out_conv
         # The plan is generated twice: a sizing pass (no allocations, no descriptors) that only
         # measures the shared scratch buffers, then the emitting pass.
         for sizing in (True, False):
@@ -421,20 +442,10 @@ class SkipEngine:
         self._sizing = sizing
         self.fwd_ops, self.bwd_ops, self.bwd_input_ops, self.keep = [], [], [], []
         if not sizing:
-            self.stats_scratch = self._new(self.stat_need)
-            self.bwd_scratch = self._new(self.bwdp_need)
-            self.wg_scratch = self._new(self.wg_need)
-            self.wgb_scratch = self._new(self.wgb_need)
-            self.wg_scratch2 = self._new(self.wg2_need)
-            self.wgb_scratch2 = self._new(self.wgb2_need)
-            self.ws_scratch = self._new(self.ws_need)
-            self.stats_scratch2 = self._new(self.stat2_need)
-            self.ws_scratch2 = self._new(self.ws2_need)
-            self.bwd_scratch2 = self._new(self.bwdp2_need)
-            self.bwd_scratch3 = self._new(self.bwdp3_need)
+            self._pool = {name: self._new(self._need[name]) for name in self._SCRATCH}
             # zero-initialised; every launch leaves its counters at zero
-            self.tickets = self._dalloc(self.ticket_need, torch.int32, zero=True)
-            self._alloc.append(self.tickets)
+            self._pool["tickets"] = self._dalloc(self._need["tickets"], torch.int32, zero=True)
+            self._alloc.append(self._pool["tickets"])
         self._ticket_off = 0
         self._fused_bnb = {}
         self._deferred = []
@@ -518,23 +529,23 @@ class SkipEngine:
     def _ticket(self, n=8):
         """n arrival counters for one in-launch finalisation (sizing pass: only counts them)."""
         if self._sizing:
-            self.ticket_need += n
+            self._need["tickets"] += n
             return None
         off = self._ticket_off
         self._ticket_off += n
-        assert self._ticket_off <= self.tickets.numel()
-        return self.tickets.data_ptr() + 4 * off
+        assert self._ticket_off <= self._need["tickets"]
+        return self._pool["tickets"].data_ptr() + 4 * off
 
     def _bn_fin(self, bn: BNRec, ticket) -> N.DipBnFin:
         m = bn.module
-        return N.DipBnFin(_ptr(self.params, bn.gamma_off), _ptr(self.params, bn.beta_off), float(m.eps), float(m.momentum),
-                          _ptr(bn.state), bn.Cs, bn.C,
-                          _ptr(self.bnbuf, bn.rm_off) if bn.rm_off >= 0 else None,
-                          _ptr(self.bnbuf, bn.rv_off) if bn.rv_off >= 0 else None, ticket)
+        return N.DipBnFin(gamma=_ptr(self.params, bn.gamma_off), beta=_ptr(self.params, bn.beta_off), eps=float(m.eps),
+                          momentum=float(m.momentum), state=_ptr(bn.state), Cs=bn.Cs, C=bn.C,
+                          running_mean=_ptr(self.bnbuf, bn.rm_off) if bn.rm_off >= 0 else None,
+                          running_var=_ptr(self.bnbuf, bn.rv_off) if bn.rv_off >= 0 else None, ticket=ticket)
 
     def _bnb_fin(self, bn: BNRec, npix, ticket) -> N.DipBnbFin:
-        return N.DipBnbFin(_ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off), _ptr(bn.coef), bn.C, npix,
-                           ticket)
+        dgamma, dbeta, coef = self._dparams(bn)
+        return N.DipBnbFin(dgamma=dgamma, dbeta=dbeta, coef=coef, C=bn.C, npix=npix, ticket=ticket)
 
     def _emit_bn_finalize(self, bn: BNRec, scratch, rows, cstride):
         """Partial rows -> state block + running statistics (dip_bn_finalize).  A separate launch on purpose: finishing
@@ -551,6 +562,11 @@ class SkipEngine:
                 _ptr(self.bnbuf, bn.rv_off) if bn.rv_off >= 0 else None)
         self.fwd_ops.append((self.lib.dip_bn_finalize, args, "bn_fin:" + bn.name))
 
+    def _bf3_ok(self, r: ConvRec, which, unless=False) -> bool:
+        """Does the bf16-pipe plan (N.conv_plan; otherwise N.conv_plan_fp32) apply to a launch of conv r: the conv has split
+        weight planes (which = "fwd3_off" | "dgrad3_off") and nothing (`unless`) keeps the launch on the fp32 kernels."""
+        return self.bf3 and getattr(r, which, -1) >= 0 and not unless
+
     def _emit_conv_fwd(self, r: ConvRec, x: Act, y, bn: Optional[BNRec]):
         assert x.C == r.Cin, (r.name, x.C, r.Cin)
         Ho = (x.H + 2 * r.P - r.ks) // r.stride + 1
@@ -558,17 +574,18 @@ class SkipEngine:
         Cy = round_up(r.Cout, 4)
         sizing = self._sizing
         # (sizing pass: the descriptor carries the shape only -- buffers are None)
-        d = N.DipConvDesc(_ptr(x.buf), x.H, x.W, x.Cs, round_up(x.C, 4), x.transform(sizing),
-                          None if sizing else _ptr(self.packed, r.fwd_off),
-                          _ptr(self.params, r.b_off) if (r.b_off >= 0 and not sizing) else None,
-                          _ptr(y), Ho, Wo, Cy, r.Cout, 0, r.ks, r.stride, r.pad_mode, r.P, 1, 0, None, 1, None)
+        d = N.DipConvDesc(x=_ptr(x.buf), Hin=x.H, Win=x.W, Cx=x.Cs, Cin=round_up(x.C, 4), tr=x.transform(sizing),
+                          wp=None if sizing else _ptr(self.packed, r.fwd_off),
+                          bias=_ptr(self.params, r.b_off) if (r.b_off >= 0 and not sizing) else None,
+                          y=_ptr(y), Hout=Ho, Wout=Wo, Cy=Cy, Cout=r.Cout, ks=r.ks, stride=r.stride, pad_mode=r.pad_mode,
+                          off=r.P, dil=1, ksplit=1)
         small = self.use_small and bool(self.lib.dip_conv_small_eligible(C.byref(d)))
         if small:
             ksplit, ntiles, wsf = 1, self.lib.dip_conv_small_rows(C.byref(d)), 0
         else:
             # (a layer the bf16-pipe kernel will not take -- no split weights, a transform over > 512 channels -- is planned for
             # the fp32 kernels: dip_conv_plan's "96..255 tiles in one pass" rule is the 64-column bf16 form's)
-            bf3_ok = self.bf3 and getattr(r, "fwd3_off", -1) >= 0 and not (x.bn is not None and round_up(x.C, 4) > 512)
+            bf3_ok = self._bf3_ok(r, "fwd3_off", unless=x.bn is not None and round_up(x.C, 4) > 512)
             plan = N.conv_plan if bf3_ok else N.conv_plan_fp32
             ksplit, ntiles, wsf = plan(Ho, Wo, round_up(x.C, 4), r.Cout, r.ks, r.stride)
         # the skip-branch convs run on the side stream next to the encoder convs of their scale
@@ -578,20 +595,12 @@ class SkipEngine:
         side = r.name.endswith("skip_conv") and Ho * Wo >= self.side_min_pixels and bn is not None
         if side:
             self._fwd_side.update(("conv_fwd:" + r.name, "bn_fin:" + bn.name))
+        stats_scratch = self._scratch("stats2" if side else "stats", ntiles * 3 * round_up(r.Cout, 32) if bn is not None else 0)
+        ws_scratch = self._scratch("ws2" if side else "ws", wsf)
         if sizing:
-            if side:
-                if bn is not None:
-                    self.stat2_need = max(self.stat2_need, ntiles * 3 * round_up(r.Cout, 32))
-                self.ws2_need = max(self.ws2_need, wsf)
-            else:
-                if bn is not None:
-                    self.stat_need = max(self.stat_need, ntiles * 3 * round_up(r.Cout, 32))
-                self.ws_need = max(self.ws_need, wsf)
             return
-        stats_scratch = self.stats_scratch2 if side else self.stats_scratch
-        ws_scratch = self.ws_scratch2 if side else self.ws_scratch
         d.stats = _ptr(stats_scratch) if bn is not None else None
-        if self.bf3 and getattr(r, "fwd3_off", -1) >= 0:
+        if self._bf3_ok(r, "fwd3_off"):
             d.wp3 = self.packed3.data_ptr() + 2 * r.fwd3_off
         d.ksplit = ksplit
         d.ws = _ptr(ws_scratch) if ksplit > 1 else None
@@ -605,12 +614,12 @@ class SkipEngine:
     def _emit_avgpool(self, x, H, W, Cc, y, bn: BNRec, kind='avg'):
         Cs = round_up(Cc, 4)
         nblk = self.lib.dip_upcat_nblk(H // 2, W // 2, Cc)
+        stats = self._scratch("stats", nblk * 3 * Cs)
         if self._sizing:
-            self.stat_need = max(self.stat_need, nblk * 3 * Cs)
             return
         fn = self.lib.dip_maxpool2_fwd if kind == 'max' else self.lib.dip_avgpool2_fwd
-        self.fwd_ops.append((fn, (_ptr(x), H, W, Cs, Cc, _ptr(y), Cs, _ptr(self.stats_scratch), nblk), "pool:" + bn.name))
-        self._emit_bn_finalize(bn, self.stats_scratch, nblk, Cs)
+        self.fwd_ops.append((fn, (_ptr(x), H, W, Cs, Cc, _ptr(y), Cs, _ptr(stats), nblk), "pool:" + bn.name))
+        self._emit_bn_finalize(bn, stats, nblk, Cs)
 
     def _emit_upcat(self, s, s_act: Optional[Act], deep: Act, cat, H, W, geom=None):
         Ccat = s.ns + deep.C
@@ -618,17 +627,15 @@ class SkipEngine:
         nblk = self.lib.dip_upcat_nblk(H, W, Ccat)
         fin_ok = self.ticket_fin and bool(self.lib.dip_fin_rows_ok(nblk, Ccat))
         ticket = self._ticket() if fin_ok else None
+        stats = self._scratch("stats", nblk * 3 * Cs_cat)
         if self._sizing:
-            self.stat_need = max(self.stat_need, nblk * 3 * Cs_cat)
             return
         mode = N.UP_BILINEAR if s.upsample_mode == "bilinear" else N.UP_NEAREST
-        d = N.DipUpcatDesc(_ptr(s_act.buf) if s_act else None, s_act.Cs if s_act else 4, s.ns,
-                           s_act.transform() if s_act else N.DipTransform(None, None, 1.0),
-                           _ptr(deep.buf), deep.Cs, deep.C, deep.transform(), H, W, mode, _ptr(cat), Cs_cat,
-                           _ptr(self.stats_scratch), nblk)
-        if geom is not None:                      # general centre crop (DipUpcatDesc: Hs / Hd geometry)
-            for k, v in geom.items():
-                setattr(d, k, v)
+        # (geom: general centre crop -- the Hs / Hd geometry fields of DipUpcatDesc, zero otherwise)
+        d = N.DipUpcatDesc(s=_ptr(s_act.buf) if s_act else None, Cs_s=s_act.Cs if s_act else 4, ns=s.ns,
+                           ts=s_act.transform() if s_act else N.DipTransform(None, None, 1.0),
+                           d=_ptr(deep.buf), Cs_d=deep.Cs, nd=deep.C, td=deep.transform(), H=H, W=W, mode=mode,
+                           cat=_ptr(cat), Cs_cat=Cs_cat, stats=_ptr(stats), nblk=nblk, **(geom or {}))
         self.keep.append(d)
         if fin_ok:      # few partial rows: the last block to arrive finalises the concat BatchNorm (bn_ticket.h)
             fin = self._bn_fin(s.cat_bn, ticket)
@@ -636,7 +643,7 @@ class SkipEngine:
             self.fwd_ops.append((self.lib.dip_upcat_fwd_fin, (C.byref(d), C.byref(fin)), "upcat:" + s.cat_bn.name))
             return
         self.fwd_ops.append((self.lib.dip_upcat_fwd, (C.byref(d),), "upcat:" + s.cat_bn.name))
-        self._emit_bn_finalize(s.cat_bn, self.stats_scratch, nblk, Cs_cat)
+        self._emit_bn_finalize(s.cat_bn, stats, nblk, Cs_cat)
 
     def _flush_deferred_wgrads(self):
         ops, self._deferred = self._deferred, []
@@ -660,22 +667,17 @@ class SkipEngine:
         if Ho * Wo <= self.bulk2_max_pixels:
             second = self._bulk_flip
             self._bulk_flip = not self._bulk_flip
+        wg = self._scratch("wg2" if second else "wg", nsplit * slab)
+        wgb = self._scratch("wgb2" if second else "wgb", nsplit * CoutP)
         if self._sizing:
-            if second:
-                self.wg2_need = max(self.wg2_need, nsplit * slab)
-                self.wgb2_need = max(self.wgb2_need, nsplit * CoutP)
-            else:
-                self.wg_need = max(self.wg_need, nsplit * slab)
-                self.wgb_need = max(self.wgb_need, nsplit * CoutP)
             return
         has_b = r.b_off >= 0
-        wg, wgb = (self.wg_scratch2, self.wgb_scratch2) if second else (self.wg_scratch, self.wgb_scratch)
         if second:
             self._bulk2.update(("wgrad:" + r.name, "wgred:" + r.name))
-        d = N.DipWgradDesc(_ptr(x.buf), x.H, x.W, x.Cs, x.C, x.transform(), _ptr(dy), Ho, Wo,
-                           round_up(r.Cout, 4), r.Cout, r.ks, r.stride, r.pad_mode, r.P,
-                           _ptr(wg), _ptr(wgb) if has_b else None, nsplit, tap_groups,
-                           chan_block)
+        d = N.DipWgradDesc(x=_ptr(x.buf), Hin=x.H, Win=x.W, Cx=x.Cs, Cin=x.C, tr=x.transform(), dy=_ptr(dy), Hout=Ho, Wout=Wo,
+                           Cdy=round_up(r.Cout, 4), Cout=r.Cout, ks=r.ks, stride=r.stride, pad_mode=r.pad_mode, off=r.P,
+                           partial=_ptr(wg), bias_partial=_ptr(wgb) if has_b else None, nsplit=nsplit,
+                           tap_groups=tap_groups, chan_block=chan_block)
         self.keep.append(d)
         ops.append((self.lib.dip_conv_wgrad, (C.byref(d),), "wgrad:" + r.name))
         ops.append((self.lib.dip_wgrad_reduce,
@@ -698,7 +700,16 @@ class SkipEngine:
         pad = r.P if reflect else 0
         Hg, Wg = x.H + 2 * pad, x.W + 2 * pad
         off = (r.ks - 1) if reflect else (r.ks - 1 - r.P)
-        Cg = x.Cs
+        Cg, Cdy = x.Cs, round_up(r.Cout, 4)
+        sizing = self._sizing
+
+        def desc(src, dst, Hy, Wy, off_y, **fields):
+            """The data gradient as a convolution: dy at address src -> the gradient on an Hy x Wy domain at address dst, with
+            r's packed data-gradient weights, zero padding and stride 1 (the sizing pass carries the shape only)."""
+            return N.DipConvDesc(x=src, Hin=Ho, Win=Wo, Cx=Cdy, Cin=Cdy, tr=N.DipTransform(None, None, 1.0),
+                                 wp=None if sizing else _ptr(self.packed, r.dgrad_off), y=dst, Hout=Hy, Wout=Wy, Cy=Cg,
+                                 Cout=r.Cin, ks=r.ks, stride=1, pad_mode=N.PAD_ZERO, off=off_y, **fields)
+
         if accumulate_into is not None:
             # the skip-branch conv (filter_skip_size, 1x1 in every notebook) reads the same input as down_a:
             # its data gradient is ADDED into down_a's (padded) gradient buffer, at the offset that aligns
@@ -707,14 +718,11 @@ class SkipEngine:
             if pad > gpad or r.stride != 1:
                 raise NotImplementedError(f"dip-amd: {r.name}: a skip filter larger than the down filter (with "
                                           "reflection padding) or a strided skip conv has no gfx950 path")
-            if self._sizing:
+            if sizing:
                 return accumulate_into
             o = gpad - pad
             Wg2 = x.W + 2 * gpad
-            ybase = _ptr(gbuf, (o * Wg2 + o) * Cg)
-            d = N.DipConvDesc(_ptr(dy), Ho, Wo, round_up(r.Cout, 4), round_up(r.Cout, 4),
-                              N.DipTransform(None, None, 1.0), _ptr(self.packed, r.dgrad_off), None,
-                              ybase, Hg, Wg, Cg, r.Cin, Wg2, r.ks, 1, N.PAD_ZERO, off, 1, 1, None)
+            d = desc(_ptr(dy), _ptr(gbuf, (o * Wg2 + o) * Cg), Hg, Wg, off, y_pitch=Wg2, dil=1, accumulate=1)
             self.keep.append(d)
             small = self.use_small and bool(self.lib.dip_conv_small_eligible(C.byref(d)))
             ops.append((self.lib.dip_conv_small if small else self.lib.dip_conv_igemm, (C.byref(d),), "dgrad+:" + r.name))
@@ -723,71 +731,47 @@ class SkipEngine:
         if reflect and r.pad_mode == N.PAD_REFLECT and r.ks == 3 and r.stride == 1 and self.use_small and need_pad == 0:
             # interior domain + a frame launch instead of the padded domain (dip_conv_dgrad_ring): no lonely second round
             # of tiles at 256^2 (561 -> 512), and the gradient buffer needs no fold
-            di = N.DipConvDesc(None, Ho, Wo, round_up(r.Cout, 4), round_up(r.Cout, 4), N.DipTransform(None, None, 1.0), None,
-                               None, None, x.H, x.W, Cg, r.Cin, 0, r.ks, 1, N.PAD_ZERO, 1, 1, 0, None, 1, None)
+            di = desc(None, None, x.H, x.W, 1, dil=1, ksplit=1)
             if self.lib.dip_conv_dgrad_ring_ok(C.byref(di)) and not self.lib.dip_conv_small_eligible(C.byref(di)):
                 ring, pad, Hg, Wg, off = True, 0, x.H, x.W, 1
         gbuf = self._buf(Hg * Wg * Cg)
+        # may phase 1 of x's BatchNorm backward ride in the epilogue of a launch of the big kernels (fuse_bnb / fuse_bnb_1x1;
+        # the low-resolution kernel decides for itself below)
+        fuse_here = (fuse_bn and x.bn is not None and not ring
+                     and (self.fuse_bnb or (self.fuse_bnb_1x1 and r.ks == 1 and r.stride == 1)))
         if r.stride == 2:
-            ksplit, _, wsf = N.conv_plan_dil2(Hg, Wg, round_up(r.Cout, 4), r.Cin, r.ks)
+            ksplit, _, wsf = N.conv_plan_dil2(Hg, Wg, Cdy, r.Cin, r.ks)
         else:
             # (fused BatchNorm-backward partials keep the layer off the bf16-pipe kernel: planned for the fp32 kernels then)
-            fuse_here = self.fuse_bnb or (self.fuse_bnb_1x1 and r.ks == 1 and r.stride == 1)
-            bf3_ok = self.bf3 and getattr(r, "dgrad3_off", -1) >= 0 and not (fuse_bn and fuse_here and not ring and x.bn is not None)
-            ksplit, _, wsf = (N.conv_plan if bf3_ok else N.conv_plan_fp32)(Hg, Wg, round_up(r.Cout, 4), r.Cin, r.ks, 1)
-        sizing = self._sizing
-        d = N.DipConvDesc(None if sizing else _ptr(dy), Ho, Wo, round_up(r.Cout, 4), round_up(r.Cout, 4),
-                          N.DipTransform(None, None, 1.0), None if sizing else _ptr(self.packed, r.dgrad_off), None,
-                          None if sizing else _ptr(gbuf), Hg, Wg, Cg, r.Cin, 0, r.ks, 1, N.PAD_ZERO, off, r.stride, 0, None,
-                          ksplit, (None if sizing else _ptr(self.ws_scratch)) if ksplit > 1 else None)
-        if self.bf3 and not sizing and getattr(r, "dgrad3_off", -1) >= 0:
-            d.wp3 = self.packed3.data_ptr() + 2 * r.dgrad3_off
+            plan = N.conv_plan if self._bf3_ok(r, "dgrad3_off", unless=fuse_here) else N.conv_plan_fp32
+            ksplit, _, wsf = plan(Hg, Wg, Cdy, r.Cin, r.ks, 1)
+        d = desc(_ptr(dy), _ptr(gbuf), Hg, Wg, off, dil=r.stride, ksplit=ksplit)
+        if not sizing:
+            if self._bf3_ok(r, "dgrad3_off"):
+                d.wp3 = self.packed3.data_ptr() + 2 * r.dgrad3_off
+            if r.pad_mode == N.PAD_REPLICATE:
+                self._replicate_bufs.add(gbuf.data_ptr())       # _gradsrc: fold = 2 (adjoint of nn.ReplicationPad2d)
         small = self.use_small and bool(self.lib.dip_conv_small_eligible(C.byref(d)))
         if small:
             # low resolution: ONE launch for all (<= 160) columns, no split-K workspace; when x feeds this conv only, phase 1
             # of its BatchNorm(+activation) backward rides in the epilogue
-            d.ksplit, d.ws = 1, None
-            rows = self.lib.dip_conv_small_rows(C.byref(d))
-            fuse = fuse_bn and x.bn is not None and r.pad_mode != N.PAD_REPLICATE and not self._bnb_one_ok(x)
-            if sizing:
-                if fuse:
-                    self.bwdp_need = max(self.bwdp_need, rows * 2 * x.bn.Cs)
-                return (gbuf, pad)
-            if r.pad_mode == N.PAD_REPLICATE:
-                self._replicate_bufs.add(gbuf.data_ptr())
-            if fuse:
-                bn = x.bn
-                d.bnb_y, d.bnb_state = _ptr(x.buf), _ptr(bn.state)
-                d.bnb_partials = _ptr(self.bwd_scratch)
-                d.bnb_Cy, d.bnb_Cs, d.bnb_pad, d.bnb_slope = x.Cs, bn.Cs, pad, float(x.slope)
-                self._fused_bnb[gbuf.data_ptr()] = (rows, 0, 0)        # -> dip_bn_bwd_finalize2 over these rows, then apply
-            self.keep.append(d)
-            ops.append((self.lib.dip_conv_small, (C.byref(d),), "dgrad:" + r.name))
+            d.ksplit = 1
+            if fuse_bn and x.bn is not None and r.pad_mode != N.PAD_REPLICATE and not self._bnb_one_ok(x):
+                self._fuse_bnb_into(d, x, gbuf, pad, self.lib.dip_conv_small_rows(C.byref(d)))
+            if not sizing:
+                self.keep.append(d)
+                ops.append((self.lib.dip_conv_small, (C.byref(d),), "dgrad:" + r.name))
             return (gbuf, pad)
+        ws = self._scratch("ws", wsf)
+        d.ws = _ptr(ws) if ksplit > 1 else None
         variant = self.lib.dip_conv_variant(C.byref(d))
-        fused = None
-        fuse_here = self.fuse_bnb or (self.fuse_bnb_1x1 and r.ks == 1 and r.stride == 1)
-        if fuse_bn and fuse_here and not ring and x.bn is not None and self.lib.dip_conv_bnb_fusable(C.byref(d)):
-            bn = x.bn
-            rows = self.lib.dip_conv_ntiles(Hg, Wg)
+        if fuse_here and self.lib.dip_conv_bnb_fusable(C.byref(d)):
             c_lo = (r.Cin - 128) if variant == 3 else 0          # columns of the conv_thin4 launch (always 4 here: % 4)
-            rows_lo = self.lib.dip_conv_thin4_ntiles(Hg, Wg) if c_lo else 0
             if c_lo % 4 == 0:
-                fused = (rows, rows_lo, c_lo)
-                self.bwdp_need = max(self.bwdp_need, rows * 2 * bn.Cs)
-                self.bwdp3_need = max(self.bwdp3_need, rows_lo * 2 * bn.Cs)
+                self._fuse_bnb_into(d, x, gbuf, pad, self.lib.dip_conv_ntiles(Hg, Wg),
+                                    self.lib.dip_conv_thin4_ntiles(Hg, Wg) if c_lo else 0, c_lo)
         if sizing:
-            self.ws_need = max(self.ws_need, wsf)
             return (gbuf, pad)
-        if r.pad_mode == N.PAD_REPLICATE:
-            self._replicate_bufs.add(gbuf.data_ptr())       # _gradsrc: fold = 2 (adjoint of nn.ReplicationPad2d)
-        if fused is not None:
-            bn = x.bn
-            d.bnb_y, d.bnb_state = _ptr(x.buf), _ptr(bn.state)
-            d.bnb_partials = _ptr(self.bwd_scratch)
-            d.bnb_partials_thin = _ptr(self.bwd_scratch3) if fused[2] else None
-            d.bnb_Cy, d.bnb_Cs, d.bnb_pad, d.bnb_slope = x.Cs, bn.Cs, pad, float(x.slope)
-            self._fused_bnb[gbuf.data_ptr()] = fused
         self.keep.append(d)
         if variant == 3 and self.two_streams:
             # 132-column data gradient = 4 thin columns on the vector ALU + 128 columns on the LDS-DMA kernel:
@@ -806,6 +790,20 @@ class SkipEngine:
             ops.append((self.lib.dip_conv_dgrad_ring, (C.byref(dr),), "dgring:" + r.name))
         return (gbuf, pad)
 
+    def _fuse_bnb_into(self, d: N.DipConvDesc, x: Act, gbuf, pad, rows, rows_lo=0, c_lo=0):
+        """Phase 1 of the BatchNorm(+activation) backward of x in the epilogue of the data-gradient launch d (DipConvDesc.bnb_*):
+        `rows` partial rows, + rows_lo of the c_lo thin columns (conv_thin4).  _emit_bn_act_bwd then finds (rows, rows_lo, c_lo)
+        under the gradient buffer and runs dip_bn_bwd_finalize2 over them instead of a statistics pass."""
+        bn = x.bn
+        partials = self._scratch("bwd", rows * 2 * bn.Cs)
+        thin = self._scratch("bwd3", rows_lo * 2 * bn.Cs)
+        if self._sizing:
+            return
+        d.bnb_y, d.bnb_state = _ptr(x.buf), _ptr(bn.state)
+        d.bnb_partials, d.bnb_partials_thin = _ptr(partials), _ptr(thin) if c_lo else None
+        d.bnb_Cy, d.bnb_Cs, d.bnb_pad, d.bnb_slope = x.Cs, bn.Cs, pad, float(x.slope)
+        self._fused_bnb[gbuf.data_ptr()] = (rows, rows_lo, c_lo)
+
     def _thin_src_ok(self, oc: ConvRec, last: Act) -> bool:
         """The net's last conv (models/skip.py:98) as a gradient source of the BatchNorm in front of it: 1x1, <= 4 output
         channels, a whole number of float4 channel groups in, and an activation above the one-launch BatchNorm backward's range
@@ -816,17 +814,50 @@ class SkipEngine:
     def _gradsrc(self, g, Cg, choff=0, window=None):
         if len(g) == 3:                           # (dy of the thin 1x1 conv, 0, its ConvRec): _thin_src_ok
             buf, _, oc = g
-            d = N.DipGradSrc(_ptr(buf), 0, 0, round_up(oc.Cout, 4), 0)
-            d.tw, d.tn, d.tcw = _ptr(self.params, oc.w_off), oc.Cout, oc.Cin
+            d = N.DipGradSrc(g=_ptr(buf), Cg=round_up(oc.Cout, 4), tw=_ptr(self.params, oc.w_off), tn=oc.Cout, tcw=oc.Cin)
             self.keep.append(d)
             return d
         buf, pad = g
         fold = 0 if pad == 0 else (2 if buf.data_ptr() in self._replicate_bufs else 1)
-        d = N.DipGradSrc(_ptr(buf), pad, fold, Cg, choff)
+        d = N.DipGradSrc(g=_ptr(buf), pad=pad, fold=fold, Cg=Cg, choff=choff)
         if window is not None:                    # (win_y, win_x, win_h, win_w): adjoint of Concat's crop of this branch
             d.win_y, d.win_x, d.win_h, d.win_w = window
         self.keep.append(d)
         return d
+
+    def _act_args(self, a: Act):
+        """The argument run that describes an activation and its BatchNorm state to the BatchNorm-backward launches."""
+        return (_ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(a.bn.state), a.bn.Cs, float(a.slope))
+
+    def _dparams(self, bn: BNRec):
+        """(dgamma, dbeta, coef): where phase 2 of a BatchNorm backward leaves the parameter gradients and the coefficients
+        of phase 3."""
+        return (_ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off), _ptr(bn.coef))
+
+    def _emit_bnb_apply(self, a: Act, dz, ops, src=None, partials=None):
+        """Phase 3 of the BatchNorm backward of `a` into dz.  src: the gradient source the masked gradient is recomputed
+        from; None: dz holds it already (the adjoint of the up-sampling wrote it).  partials = (scratch, rows): phase 2 rides
+        in the launch's prologue -- every block reduces the few partial rows, no finalisation launch."""
+        bn, lib = a.bn, self.lib
+        if partials is None:
+            fns, fin = (lib.dip_bn_bwd_apply, lib.dip_bn_bwd_apply_src), (_ptr(bn.coef),)
+        else:
+            fns = (lib.dip_bn_bwd_apply_fin, lib.dip_bn_bwd_apply_src_fin)
+            fin = (_ptr(partials[0]), partials[1], *self._dparams(bn))
+        if src is None:
+            args = (_ptr(dz), a.Cs, _ptr(a.buf), a.Cs, a.H * a.W, a.C, _ptr(bn.state), bn.Cs, *fin)
+        else:
+            args = (C.byref(src), *self._act_args(a), *fin, _ptr(dz), a.Cs)
+        ops.append((fns[src is not None], args, "bnb_apply:" + bn.name))
+
+    def _emit_bnb_fin_apply(self, a: Act, scratch, rows, dz, ops, src=None):
+        """Phases 2 and 3 of the BatchNorm backward of `a` from the `rows` partial rows that phase 1 left in scratch."""
+        bn = a.bn
+        if self._fin_rows_ok(rows, a.C):
+            return self._emit_bnb_apply(a, dz, ops, src, (scratch, rows))
+        ops.append((self.lib.dip_bn_bwd_finalize, (_ptr(scratch), rows, bn.Cs, bn.C, a.H * a.W, *self._dparams(bn)),
+                    "bnb_fin:" + bn.name))
+        self._emit_bnb_apply(a, dz, ops, src)
 
     def _emit_bn_act_bwd(self, a: Act, g, ops, choff=0, Cg=None, side=False, window=None):
         """BatchNorm(+LeakyReLU) backward of activation `a` given the gradient source g=(buf,pad)
@@ -836,65 +867,45 @@ class SkipEngine:
         nblk = self.lib.dip_bn_bwd_nblk(a.H, a.W, a.C)
         fin_ok = self.ticket_fin and bool(self.lib.dip_fin_rows_ok(nblk, a.C))
         ticket = self._ticket() if fin_ok else None      # (unused when the data gradient carried the statistics)
+        scratch = self._scratch("bwd2" if side else "bwd", nblk * 2 * a.Cs)
         if self._sizing:
-            if side:
-                self.bwdp2_need = max(self.bwdp2_need, nblk * 2 * a.Cs)
-            else:
-                self.bwdp_need = max(self.bwdp_need, nblk * 2 * a.Cs)
             return None
-        scratch = self.bwd_scratch2 if side else self.bwd_scratch
         dz = self._new(a.H * a.W * a.Cs)
         src = self._gradsrc(g, Cg if Cg is not None else a.Cs, choff, window)
         lib = self.lib
         if self._bnb_one_ok(a) and self._fused_bnb.get(g[0].data_ptr()) is None:
             # low resolution: statistics, finalisation and apply in ONE launch (a workgroup owns 4 channels of the plane)
-            ops.append((lib.dip_bn_bwd_one, (C.byref(src), _ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(bn.state), bn.Cs,
-                                             float(a.slope), _ptr(dz), a.Cs, _ptr(self.grads, bn.gamma_off),
-                                             _ptr(self.grads, bn.beta_off), _ptr(bn.coef)), "bnb_one:" + bn.name))
+            ops.append((lib.dip_bn_bwd_one, (C.byref(src), *self._act_args(a), _ptr(dz), a.Cs, *self._dparams(bn)),
+                        "bnb_one:" + bn.name))
             return dz
         # phase 1 only reduces (dz = NULL); phase 3 recomputes the masked gradient from the source:
         # 5 tensor passes per BatchNorm instead of 6
+        stats = (C.byref(src), *self._act_args(a), None, a.Cs, _ptr(scratch), nblk)
         fused = self._fused_bnb.get(g[0].data_ptr()) if (choff == 0 and not side) else None
         if fused is None and fin_ok:
             # few partial rows: phase 2 rides in the statistics launch (the last block to arrive reduces them)
             fin = self._bnb_fin(bn, a.H * a.W, ticket)
             self.keep.append(fin)
-            ops.append((lib.dip_bn_bwd_stats_fin, (C.byref(src), _ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(bn.state), bn.Cs,
-                                                   float(a.slope), None, a.Cs, _ptr(scratch), nblk, C.byref(fin)),
-                        "bnb_stats:" + bn.name))
-        elif fused is not None:
-            # phase 1 already ran in the epilogue of the data-gradient launch(es) that produced g (_emit_dgrad)
+            ops.append((lib.dip_bn_bwd_stats_fin, (*stats, C.byref(fin)), "bnb_stats:" + bn.name))
+            self._emit_bnb_apply(a, dz, ops, src)
+        elif fused is None:
+            ops.append((lib.dip_bn_bwd_stats, stats, "bnb_stats:" + bn.name))
+            self._emit_bnb_fin_apply(a, scratch, nblk, dz, ops, src)
+        else:
+            # phase 1 already ran in the epilogue of the data-gradient launch(es) that produced g (_fuse_bnb_into: the partial
+            # rows are in the main stream's scratch, the thin columns' in "bwd3")
             rows, rows_lo, c_lo = fused
             if c_lo == 0 and self._fin_rows_ok(rows, a.C):
-                ops.append(self._apply_src_fin(src, a, bn, self.bwd_scratch, rows, dz))
+                self._emit_bnb_apply(a, dz, ops, src, (scratch, rows))
                 return dz
-            ops.append((lib.dip_bn_bwd_finalize2, (_ptr(self.bwd_scratch), rows, _ptr(self.bwd_scratch3) if c_lo else None,
-                                                   rows_lo, c_lo, bn.Cs, bn.C, a.H * a.W,
-                                                   _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off),
-                                                   _ptr(bn.coef)), "bnb_fin:" + bn.name))
-        else:
-            ops.append((lib.dip_bn_bwd_stats, (C.byref(src), _ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(bn.state), bn.Cs,
-                                               float(a.slope), None, a.Cs, _ptr(scratch), nblk),
-                        "bnb_stats:" + bn.name))
-            if self._fin_rows_ok(nblk, a.C):
-                # few partial rows: every block of the apply launch reduces them in its prologue (no finalisation launch)
-                ops.append(self._apply_src_fin(src, a, bn, scratch, nblk, dz))
-                return dz
-            ops.append((lib.dip_bn_bwd_finalize, (_ptr(scratch), nblk, bn.Cs, bn.C, a.H * a.W,
-                                                  _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off),
-                                                  _ptr(bn.coef)), "bnb_fin:" + bn.name))
-        ops.append((lib.dip_bn_bwd_apply_src, (C.byref(src), _ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(bn.state), bn.Cs,
-                                               float(a.slope), _ptr(bn.coef), _ptr(dz), a.Cs), "bnb_apply:" + bn.name))
+            thin = self._scratch("bwd3", rows_lo * 2 * bn.Cs) if c_lo else None
+            ops.append((lib.dip_bn_bwd_finalize2, (_ptr(scratch), rows, _ptr(thin), rows_lo, c_lo, bn.Cs, bn.C, a.H * a.W,
+                                                   *self._dparams(bn)), "bnb_fin:" + bn.name))
+            self._emit_bnb_apply(a, dz, ops, src)
         return dz
 
     def _fin_rows_ok(self, rows, Cc) -> bool:
         return self.bnb_fin_fuse and bool(self.lib.dip_bn_bwd_fin_rows_ok(rows, Cc))
-
-    def _apply_src_fin(self, src, a: Act, bn: BNRec, scratch, rows, dz):
-        return (self.lib.dip_bn_bwd_apply_src_fin,
-                (C.byref(src), _ptr(a.buf), a.H, a.W, a.Cs, a.C, _ptr(bn.state), bn.Cs, float(a.slope), _ptr(scratch), rows,
-                 _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off), _ptr(bn.coef), _ptr(dz), a.Cs),
-                "bnb_apply:" + bn.name)
 
     def _bnb_one_ok(self, a: Act) -> bool:
         return self.bnb_one and a.bn is not None and bool(self.lib.dip_bn_bwd_one_ok(a.H * a.W, a.C))
@@ -904,52 +915,34 @@ class SkipEngine:
         nblk = self.lib.dip_bn_bwd_nblk(deep.H, deep.W, deep.C)
         fin_ok = self.ticket_fin and bool(self.lib.dip_fin_rows_ok(nblk, deep.C))
         ticket = self._ticket() if fin_ok else None
+        scratch = self._scratch("bwd", nblk * 2 * deep.Cs)
         if self._sizing:
-            self.bwdp_need = max(self.bwdp_need, nblk * 2 * deep.Cs)
             return None
         dz = self._new(deep.H * deep.W * deep.Cs)
         lib = self.lib
         m = N.UP_BILINEAR if mode == "bilinear" else N.UP_NEAREST
+        # the argument runs of the up-sampling adjoints: the concat gradient + the crop geometry (default: that of the 2x2-block
+        # kernels, _plan_scale), then the deeper branch's activation, BatchNorm state and dz
+        gm = geom if geom is not None else dict(Hd=(H + 1) // 2, Wd=(W + 1) // 2, od_y=0, od_x=0)
+        crop = (_ptr(dcat), Cs_cat, choff, H, W, gm["Hd"], gm["Wd"], gm["od_y"], gm["od_x"], m)
+        act = (_ptr(deep.buf), deep.Cs, deep.C, _ptr(bn.state), bn.Cs, float(deep.slope), _ptr(dz), deep.Cs)
         if self._bnb_one_ok(deep):
             # low resolution: adjoint of the up-sampling + the three BatchNorm-backward phases of the deeper branch in ONE launch
-            gm = geom if geom is not None else dict(Hd=(H + 1) // 2, Wd=(W + 1) // 2, od_y=0, od_x=0)
-            ops.append((lib.dip_upsample_bwd_one,
-                        (_ptr(dcat), Cs_cat, choff, H, W, gm["Hd"], gm["Wd"], gm["od_y"], gm["od_x"], m, _ptr(deep.buf),
-                         deep.Cs, deep.C, _ptr(bn.state), bn.Cs, float(deep.slope), _ptr(dz), deep.Cs,
-                         _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off), _ptr(bn.coef)), "upb_one:" + bn.name))
-            return dz
-        if fin_ok:
+            ops.append((lib.dip_upsample_bwd_one, (*crop, *act, *self._dparams(bn)), "upb_one:" + bn.name))
+        elif fin_ok:
             # adjoint of the up-sampling + phases 1 and 2 of the deeper branch's BatchNorm backward in one launch
             fin = self._bnb_fin(bn, deep.H * deep.W, ticket)
             self.keep.append(fin)
-            gm = geom if geom is not None else dict(Hd=(H + 1) // 2, Wd=(W + 1) // 2, od_y=0, od_x=0)
-            ops.append((lib.dip_upsample_bwd_stats_crop_fin,
-                        (_ptr(dcat), Cs_cat, choff, H, W, gm["Hd"], gm["Wd"], gm["od_y"], gm["od_x"], m,
-                         _ptr(deep.buf), deep.Cs, deep.C, _ptr(bn.state), bn.Cs, float(deep.slope), _ptr(dz), deep.Cs,
-                         _ptr(self.bwd_scratch), nblk, C.byref(fin)), "upb_stats:" + bn.name))
-            ops.append((lib.dip_bn_bwd_apply, (_ptr(dz), deep.Cs, _ptr(deep.buf), deep.Cs, deep.H * deep.W, deep.C,
-                                               _ptr(bn.state), bn.Cs, _ptr(bn.coef)), "bnb_apply:" + bn.name))
-            return dz
-        if geom is None:
-            ops.append((lib.dip_upsample_bwd_stats, (_ptr(dcat), Cs_cat, choff, H, W, m, _ptr(deep.buf), deep.Cs, deep.C,
-                                                     _ptr(bn.state), bn.Cs, float(deep.slope), _ptr(dz), deep.Cs,
-                                                     _ptr(self.bwd_scratch), nblk), "upb_stats:" + bn.name))
+            ops.append((lib.dip_upsample_bwd_stats_crop_fin, (*crop, *act, _ptr(scratch), nblk, C.byref(fin)),
+                        "upb_stats:" + bn.name))
+            self._emit_bnb_apply(deep, dz, ops)
         else:
-            ops.append((lib.dip_upsample_bwd_stats_crop,
-                        (_ptr(dcat), Cs_cat, choff, H, W, geom["Hd"], geom["Wd"], geom["od_y"], geom["od_x"], m,
-                         _ptr(deep.buf), deep.Cs, deep.C, _ptr(bn.state), bn.Cs, float(deep.slope), _ptr(dz), deep.Cs,
-                         _ptr(self.bwd_scratch), nblk), "upb_stats:" + bn.name))
-        if self._fin_rows_ok(nblk, deep.C):
-            ops.append((lib.dip_bn_bwd_apply_fin, (_ptr(dz), deep.Cs, _ptr(deep.buf), deep.Cs, deep.H * deep.W, deep.C,
-                                                   _ptr(bn.state), bn.Cs, _ptr(self.bwd_scratch), nblk,
-                                                   _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off),
-                                                   _ptr(bn.coef)), "bnb_apply:" + bn.name))
-            return dz
-        ops.append((lib.dip_bn_bwd_finalize, (_ptr(self.bwd_scratch), nblk, bn.Cs, bn.C, deep.H * deep.W,
-                                              _ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off),
-                                              _ptr(bn.coef)), "bnb_fin:" + bn.name))
-        ops.append((lib.dip_bn_bwd_apply, (_ptr(dz), deep.Cs, _ptr(deep.buf), deep.Cs, deep.H * deep.W, deep.C,
-                                           _ptr(bn.state), bn.Cs, _ptr(bn.coef)), "bnb_apply:" + bn.name))
+            if geom is None:
+                ops.append((lib.dip_upsample_bwd_stats, (_ptr(dcat), Cs_cat, choff, H, W, m, *act, _ptr(scratch), nblk),
+                            "upb_stats:" + bn.name))
+            else:
+                ops.append((lib.dip_upsample_bwd_stats_crop, (*crop, *act, _ptr(scratch), nblk), "upb_stats:" + bn.name))
+            self._emit_bnb_fin_apply(deep, scratch, nblk, dz, ops)
         return dz
 
     def _bwd_scale_ops(self, i, dy_last):
@@ -1362,7 +1355,7 @@ class SkipEngine:
             if need_input_grad:
                 self._issue(self.bwd_input_ops, main, "bwdin")
                 gbuf, pad = self._input_gin()
-                src = N.DipGradSrc(_ptr(gbuf), pad, 1 if pad > 0 else 0, round_up(self.Cimg, 4), 0)
+                src = N.DipGradSrc(g=_ptr(gbuf), pad=pad, fold=1 if pad > 0 else 0, Cg=round_up(self.Cimg, 4))
                 gx = torch.empty((1, self.Cimg, H, W), dtype=torch.float32, device=dev)
                 N.check(lib.dip_fold_to_nchw(C.byref(src), H, W, self.Cimg, gx.data_ptr(), stream), "fold_to_nchw")
         # NOTE: the returned gradients are VIEWS of the gradient arena; the next backward() overwrites
@@ -1452,6 +1445,10 @@ class ResNetEngine(SkipEngine):
     def _input_gin(self):
         return self.gin
 
+    def _has_big_layer(self, H, W) -> bool:
+        # SkipEngine's rule applied to this net's layers (all 3x3, all at full resolution)
+        return any(r.Cin >= 96 and r.Cout >= 96 and H * W >= 65536 for r in self.convs)
+
     # ------------------------------------------------------------------ join emitters
     def _emit_join_fwd(self, xa: Act, xb: Act, out, name):
         if self._sizing:
@@ -1482,17 +1479,8 @@ class ResNetEngine(SkipEngine):
     def _build_plan(self, H, W, Cin_img):
         if min(H, W) < 2:
             raise NotImplementedError(f"dip-amd: input {H}x{W} is too small for a padded 3x3 convolution")
-        self.H, self.W, self.Cimg = H, W, Cin_img
-        self._clists = {}
-        self._reset_sizing()
-        self._alloc = []
+        self._begin_plan(H, W, Cin_img)
         oc = self.out_conv
-        self.n_out = oc.Cout
-        if getattr(self, "_bulk2_auto", self.bulk2_max_pixels < 0):
-            # SkipEngine's rule applied to this net's layers: a second bulk stream iff no conv is a big MFMA-bound layer
-            self._bulk2_auto = True
-            big = any(r.Cin >= 96 and r.Cout >= 96 and H * W >= 65536 for r in self.convs)
-            self.bulk2_max_pixels = 0 if big else 100000
         Cc = self.first.Cout
         n = H * W * round_up(Cc, 4)
         for sizing in (True, False):

@@ -61,8 +61,8 @@ def test_planner_launch_lists(built):
     from dip_engine import Act
     last = eng._plan_scale(0, Act(None, 512, 512, 32), 512, 512)
     assert (last.H, last.W, last.C) == (512, 512, 128)
-    assert eng.stat_need >= 2048 * 3 * 128
-    assert eng.ws_need > 4            # the low-resolution scales run split-K
+    assert eng._need["stats"] >= 2048 * 3 * 128
+    assert eng._need["ws"] > 4        # the low-resolution scales run split-K
     import dip_native as N
     assert N.conv_plan(512, 512, 132, 128, 3, 1) == (1, 2048, 0)
     k, rows, wsf = N.conv_plan(16, 16, 128, 128, 3, 1)
