@@ -38,8 +38,9 @@ dip_sr_tv_loss_bwd -- with the weight ONE float of every instance's slab, so a T
 
 One float serves all instances; None or all zeros is the group above; zero and positive weights do not mix.
 
-The rest of the denoising / restoration closure (denoising.ipynb:214-248, restoration.ipynb:192-211: the exponential average
-of the output, three PSNRs, the parameter checkpoint and the 5 dB fall-back), per fit and with no Python between the iterations:
+The rest of the denoising closure (denoising.ipynb:214-248: the exponential average of the output, three PSNRs, the parameter
+checkpoint and the 5 dB fall-back; restoration.ipynb:192-211 is GroupedRestorationFitMonitor, below), per fit and with no Python
+between the iterations:
 `monitor=utils.fit_monitor.GroupedFitMonitor(imgs_gt, ...)`.  The monitor's state -- gt, out_avg, partial sums, records, state,
 counter, snapshot -- is per-instance data of the slab like the targets; dip_fit_monitor_dev and dip_arena_backtrack are issued
 inside the group bracket after the backward pass and before Adam (where monitor.update(out, loss) stands in the eager closure),
@@ -63,6 +64,20 @@ records are bit-identical to the solo NativeIteration + SRFitMonitor fit; the fi
     mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)
     g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, reg_noise_std=0.03, monitor=mon)
     g.capture(); g.run(num_iter - 3); mon.history()        # [B, iters, 5]: loss, mse_LR, mse_HR, psnr_LR, psnr_HR
+
+A masked group (masks=[...]: the restoration / inpainting closure, restoration.ipynb:180-219) takes
+`monitor=utils.fit_monitor.GroupedRestorationFitMonitor(show_every=50, backtrack_db=5.0, ...)`: psrn_masked and psrn per fit and
+iteration (restoration.ipynb:192-193) and, ON every show_every-th iteration, the fall-back to the last checkpoint when psrn_masked
+dropped by more than 5 dB or else the checkpoint (:198-211).  Its descriptor points at the slab's own target and mask rows (no
+second copy of either); partial sums, records, state, counter and -- with back-tracking -- the snapshot are per-instance data of
+the slab behind everything a monitor-less masked group owns.  ONE dip_restore_monitor_dev and ONE dip_arena_backtrack call inside
+the group bracket, after the backward pass and before Adam, serve all B inside the ONE hipGraph of capture(); every instance
+takes its own decision and is bit-identical to the solo NativeIteration + RestorationFitMonitor fit.  It needs masks=, is not
+combined with downsamplers= or exp_weight= / ema_init= (this closure has no moving average: out_avg stays None).
+
+    mon = GroupedRestorationFitMonitor(show_every=50, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs, masks=masks, monitor=mon)
+    g.capture(); g.run(num_iter - 3); mon.history()        # [B, iters, 6]: loss, mse_masked, mse, psrn_masked, psrn, fell_back
 
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
@@ -123,14 +138,16 @@ class GroupedFits:
         monitor: None, or a utils.fit_monitor.GroupedFitMonitor: EMA, PSNR records and back-tracking per instance, inside
         the launch list (then exp_weight / ema_init stay at their defaults: the monitor carries the weight and starts from
         the first output, as FitMonitor does); with downsamplers= a utils.fit_monitor.GroupedSRFitMonitor: the psnr_LR /
-        psnr_HR record per instance (no moving average: exp_weight / ema_init stay at their defaults, out_avg stays None).
+        psnr_HR record per instance (no moving average: exp_weight / ema_init stay at their defaults, out_avg stays None); with
+        masks= a utils.fit_monitor.GroupedRestorationFitMonitor: psrn_masked / psrn records and back-tracking per instance
+        (restoration.ipynb:192-211; no moving average either).
         tv_weights (with downsamplers= only): None, one float for all instances or B floats -- total_loss = mse(out_LR, img_LR)
         + tv_weights[b] * tv_loss(out_HR, tv_beta), the tail of SRHead(tv_weight=); all zero = None; a mix of zero and positive
         weights is refused (an instance with weight 0 on the TV path would differ from its solo fit where s == 0)."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
-        self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets)
+        self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
@@ -233,9 +250,11 @@ class GroupedFits:
             if mon is not None:
                 views = dict(records=self._strided(ex["mon_records"], mon.capacity, len(mon.COLUMNS)),
                              counter=self._strided(ex["mon_counter"]))
-                if self.downsamplers is None:
+                if "mon_avg" in ex:                          # GroupedFitMonitor: the monitor carries the moving average
                     self.out_avg = self._strided(ex["mon_avg"], *hr)
-                    views.update(state=self._strided(ex["mon_state"], 4), out_avg=self.out_avg,
+                    views.update(out_avg=self.out_avg)
+                if "mon_state" in ex:                        # the back-tracking monitors (denoising, restoration)
+                    views.update(state=self._strided(ex["mon_state"], 4),
                                  snapshot=self._strided(ex["mon_snapshot"], eng.n_arena))
                 mon._adopt(self, **views)
             self._nbt_all = self._strided(eng.nbt, eng.nbt.numel())
@@ -247,15 +266,24 @@ class GroupedFits:
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
 
     @staticmethod
-    def _check_monitor(monitor, downsamplers, exp_weight, ema_init, targets):
+    def _check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks=None):
         """What can be said about `monitor` before anything is planned or allocated."""
         if monitor is None:
             return None
-        from utils.fit_monitor import GroupedFitMonitor, GroupedSRFitMonitor
-        if not isinstance(monitor, (GroupedFitMonitor, GroupedSRFitMonitor)):
-            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor or "
-                            f"None, got {type(monitor).__name__} (a solo FitMonitor cannot checkpoint a slab row)")
-        sr = isinstance(monitor, GroupedSRFitMonitor)
+        from utils.fit_monitor import GroupedFitMonitor, GroupedRestorationFitMonitor, GroupedSRFitMonitor
+        if not isinstance(monitor, (GroupedFitMonitor, GroupedSRFitMonitor, GroupedRestorationFitMonitor)):
+            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor, a "
+                            f"GroupedRestorationFitMonitor or None, got {type(monitor).__name__} (a solo FitMonitor cannot "
+                            "checkpoint a slab row)")
+        sr, restore = isinstance(monitor, GroupedSRFitMonitor), isinstance(monitor, GroupedRestorationFitMonitor)
+        if restore and downsamplers is not None:
+            raise NotImplementedError("dip-amd: GroupedFits(monitor=GroupedRestorationFitMonitor) with downsamplers= is not "
+                                      "implemented (the restoration closure has a mask and no down-sampler; the super-resolution "
+                                      "closure's record is utils.fit_monitor.GroupedSRFitMonitor)")
+        if restore and (masks is None or any(m is None for m in masks)):
+            raise ValueError("dip-amd: a GroupedRestorationFitMonitor records psrn_masked of a masked group: it needs "
+                             "GroupedFits(masks=[...]), one mask per instance (the denoising closure's monitor is "
+                             "GroupedFitMonitor)")
         if downsamplers is not None and not sr:
             raise NotImplementedError("dip-amd: GroupedFits(monitor=GroupedFitMonitor) with downsamplers= is not implemented (the "
                                       "super-resolution closure records psnr_LR / psnr_HR on two sizes: another record, "
@@ -266,13 +294,14 @@ class GroupedFits:
         if exp_weight is not None or ema_init != "first":
             raise ValueError("dip-amd: GroupedFits: exp_weight= / ema_init= are not combined with monitor= (" +
                              ("the super-resolution closure has no moving average of the output)" if sr else
+                              "the restoration closure has no moving average of the output)" if restore else
                               "the monitor carries exp_weight and starts out_avg from the first output)"))
         if monitor._adopted:
             raise RuntimeError(f"dip-amd: this {type(monitor).__name__} already belongs to a GroupedFits (a monitor is adopted "
                                "once)")
         if sr:
             monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _build_row0_monitor)
-        else:
+        elif not restore:                               # (the restoration monitor brings no images: target and mask are the group's)
             monitor._check_targets(targets)
         return monitor
 
@@ -465,6 +494,19 @@ class GroupedFits:
                                                    ex["mon_records"], ex["mon_counter"], ex["loss"])
             self._mon = FM.sr_monitor_launches(lib, self._mdesc)
             return
+        snapshot_ptr = lambda: None if ex["mon_snapshot"] is None else ex["mon_snapshot"].data_ptr()
+        if isinstance(m, FM.GroupedRestorationFitMonitor):
+            # (restoration.ipynb:192-211; img and mask are the group's own target and mask rows: no second copy)
+            ex["mon_partial"] = slab.alloc(2 * lib.dip_fit_monitor_nblk(nout))
+            ex["mon_records"] = slab.alloc(m.capacity * 6, zero=True)
+            ex["mon_state"] = slab.alloc(4, zero=True)
+            ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
+            ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
+            self._mdesc = FM.restore_monitor_descriptor(m, ex["out"], ex["target"], ex["mask"], self.mask_c, eng.Hout * eng.Wout,
+                                                        ex["mon_partial"], ex["mon_records"], ex["mon_counter"], ex["mon_state"],
+                                                        ex["loss"])
+            self._mon = FM.restore_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena, snapshot_ptr())
+            return
         ex["mon_gt"] = slab.alloc(nout) if m.imgs_gt is not None else None
         ex["mon_avg"] = slab.alloc(nout, zero=True)
         ex["mon_partial"] = slab.alloc(4 * lib.dip_fit_monitor_nblk(nout))
@@ -474,8 +516,7 @@ class GroupedFits:
         ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
         self._mdesc = FM.fit_monitor_descriptor(m, ex["out"], ex["target"], ex["mon_gt"], ex["mon_avg"], ex["mon_partial"],
                                                 ex["mon_records"], ex["mon_counter"], ex["mon_state"], ex["loss"])
-        self._mon = FM.fit_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena,
-                                            None if ex["mon_snapshot"] is None else ex["mon_snapshot"].data_ptr())
+        self._mon = FM.fit_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena, snapshot_ptr())
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()

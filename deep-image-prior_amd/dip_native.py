@@ -134,6 +134,13 @@ class DipSRMonitorDesc(C.Structure):
                 ("records", C.c_void_p), ("capacity", C.c_int32), ("reserved", C.c_int32), ("counter", C.c_void_p)]
 
 
+class DipRestoreMonitorDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("img", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int64), ("hw", C.c_int64),
+                ("mask_c", C.c_int32), ("backtrack_db", C.c_float), ("loss", C.c_void_p), ("partial", C.c_void_p),
+                ("records", C.c_void_p), ("capacity", C.c_int32), ("show_every", C.c_int32), ("backtracking", C.c_int32),
+                ("reserved", C.c_int32), ("counter", C.c_void_p), ("state", C.c_void_p)]
+
+
 _SIGS = {
     "dip_abi_version": (C.c_int, []),
     "dip_build_id": (C.c_char_p, []),
@@ -281,6 +288,9 @@ _SIGS = {
     "dip_sr_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "dip_sr_monitor_dev": (C.c_int, [C.POINTER(DipSRMonitorDesc), C.c_void_p]),
+    "dip_restore_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "dip_restore_monitor_dev": (C.c_int, [C.POINTER(DipRestoreMonitorDesc), C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),
     "dip_lanczos_down_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -320,8 +320,9 @@ class NativeIteration:
     slot of them is iteration-invariant; the ONE value that changes per iteration -- where the loss scalar goes -- is a field
     of the loss-head descriptor this object owns, which the library reads when it launches.
 
-    monitor=FitMonitor(...) adds the rest of the denoising / restoration closure (denoising.ipynb:214-248, restoration.ipynb:192-211:
-    the exponential average of the output, the three PSNRs, the back-tracking checkpoint and fall-back) to the same call: one
+    monitor=FitMonitor(...) adds the rest of the denoising closure (denoising.ipynb:214-248: the exponential average of the
+    output, the three PSNRs, the back-tracking checkpoint and fall-back; restoration.ipynb:192-211 is RestorationFitMonitor,
+    below) to the same call: one
     more command array on the main stream between the backward list and Adam -- where `monitor.update(out, loss)` stands in the
     eager closure, after backward() and before opt.step() -- holding dip_fit_monitor_dev and, for a back-tracking monitor,
     dip_arena_backtrack.  dip_fit_monitor_dev reads the iteration index from `monitor.counter` in device memory (first =
@@ -350,6 +351,19 @@ class NativeIteration:
         monitor = SRFitMonitor(img_LR, img_HR, capacity=num_iter)
         it = NativeIteration(net, SRHead(net, img_LR, downsampler), opt, net_input, reg_noise=reg, monitor=monitor)
         it.run(num_iter); psnr_history = monitor.history()[:, 3:5]
+
+    monitor=RestorationFitMonitor(net, img, mask) is the bookkeeping of the restoration / inpainting closure
+    (restoration.ipynb:192-211: psrn_masked and psrn in every iteration; ON every show_every-th iteration the fall-back to the
+    last checkpoint when psrn_masked dropped by more than 5 dB, or else the checkpoint) in the same slot and the same shape
+    as FitMonitor's: dip_restore_monitor_dev -- its descriptor points at `it.out` and the monitor's image and mask, reads the
+    iteration index from `monitor.counter` (check = i % show_every == 0, record row i) and advances it -- and, for a
+    back-tracking monitor, dip_arena_backtrack.  The head is usually MSEHead(net, img, mask=mask); the monitor keeps its own
+    mask ([1,1|C,H,W]) and asks nothing of the head.  Bit-identical to the eager closure with monitor.update(out, loss); the
+    two may alternate on one monitor.
+
+        monitor = RestorationFitMonitor(net, img_var, mask_var, show_every=50, capacity=num_iter)
+        it = NativeIteration(net, MSEHead(net, img_var, mask=mask_var), opt, net_input, reg_noise=reg, monitor=monitor)
+        it.run(num_iter); monitor.history()           # [iters, 6]: loss, mse_masked, mse, psrn_masked, psrn, fell_back
 
     step() / run(n) past the monitor's capacity raise before anything is issued.  The monitor's buffers and settings are
     part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt)."""
@@ -419,13 +433,13 @@ class NativeIteration:
 
     def _check_monitor(self):
         """What can be said about `monitor` before the output size is known (the image shape: _build)."""
-        from utils.fit_monitor import FitMonitor, SRFitMonitor
+        from utils.fit_monitor import FitMonitor, RestorationFitMonitor, SRFitMonitor
         m = self.monitor
         if m is None:
             return
-        if not isinstance(m, (FitMonitor, SRFitMonitor)):
-            raise TypeError("dip-amd: monitor must be a utils.fit_monitor.FitMonitor, an SRFitMonitor or None, got "
-                            f"{type(m).__name__}")
+        if not isinstance(m, (FitMonitor, SRFitMonitor, RestorationFitMonitor)):
+            raise TypeError("dip-amd: monitor must be a utils.fit_monitor.FitMonitor, an SRFitMonitor, a RestorationFitMonitor or "
+                            f"None, got {type(m).__name__}")
         head = getattr(self, "head", None)
         if head is not None and m.head_kind not in (None, head.kind):
             raise TypeError(f"dip-amd: an SRFitMonitor records out_LR and out_HR of a utils.loss_head.SRHead, the head is a "
@@ -433,7 +447,7 @@ class NativeIteration:
         if m.dev != self.device:
             raise RuntimeError(f"dip-amd: the {type(m).__name__} lives on {m.dev}, the iteration runs on {self.device}")
         if m.engine is not None and m.engine is not self.engine:
-            raise ValueError("dip-amd: the FitMonitor back-tracks another net (it was built for a different skip() net)")
+            raise ValueError(f"dip-amd: the {type(m).__name__} back-tracks another net (it was built for a different skip() net)")
 
     # -------------------------------------------------------------------------------------------- the command arrays
     def _signature(self, sig):

@@ -1,6 +1,6 @@
 """Device-side bookkeeping for the notebooks' closures (no counterpart file in the reference: the
-reference does this work inline, on the host, in every closure -- denoising.ipynb:214-248,
-restoration.ipynb:192-211).
+reference does this work inline, on the host, in every closure -- denoising.ipynb:214-248 (FitMonitor),
+super-resolution.ipynb:188-191 (SRFitMonitor), restoration.ipynb:192-211 (RestorationFitMonitor)).
 
     monitor = FitMonitor(net, img_noisy_torch, img_torch, exp_weight=0.99, show_every=100)
     def closure():
@@ -55,6 +55,27 @@ psnr_LR, psnr_HR; img_HR is optional):
     mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)                           # B fits: settings only, adopted once
     g = GroupedFits(nets, net_inputs, imgs_LR, downsamplers=downs, monitor=mon)     # ONE dip_sr_monitor_dev call for all B,
     g.capture(); g.run(num_iter - 3); mon.history()                                 # part of the ONE hipGraph; [B, iters, 5]
+
+The restoration / inpainting closure (restoration.ipynb:180-219) keeps a third record: psrn_masked = compare_psnr(img_masked,
+out * img_mask_np) and psrn = compare_psnr(img_np, out) on the host in every iteration (:192-193), and ON every show_every-th
+iteration (:198 `i % show_every == 0`; the denoising notebook checks between them) the fall-back to the last parameter
+checkpoint when psrn_masked dropped by more than 5 dB (:202-208), or else a copy of every parameter to the CPU (:209-211).  It
+has no EMA.  RestorationFitMonitor is that bookkeeping on the device (dip_restore_monitor: one streaming pass, a one-block
+finalize, then dip_arena_backtrack; columns loss, mse_masked, mse, psrn_masked, psrn, fell_back):
+
+    mon = RestorationFitMonitor(net, img_var, mask_var, show_every=50, capacity=num_iter)
+    def closure():
+        total_loss, out = head(net_input)                    # head = utils.loss_head.MSEHead(net, img_var, mask=mask_var)
+        total_loss.backward()
+        mon.update(out, total_loss)                          # no host sync, no parameter copy to the CPU
+        return total_loss
+
+    it = NativeIteration(net, head, opt, net_input, reg_noise=reg, monitor=mon)     # dip_restore_monitor_dev + dip_arena_backtrack,
+    it.run(n); mon.last()["psrn_masked"]                                           # indexed by mon.counter
+
+    mon = GroupedRestorationFitMonitor(show_every=50, capacity=num_iter)            # B fits: settings only, adopted once
+    g = GroupedFits(nets, net_inputs, imgs, masks=masks, monitor=mon)               # ONE dip_restore_monitor_dev and ONE
+    g.capture(); g.run(num_iter - 3); mon.history()                                 # dip_arena_backtrack call; [B, iters, 6]
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
 """
@@ -98,6 +119,32 @@ def sr_monitor_launches(lib, desc):
     return [(lib.dip_sr_monitor_dev, (C.byref(desc),), "sr_monitor_dev")]
 
 
+def restore_monitor_descriptor(m, out, img, mask, mask_c, hw, partial, records, counter, state, loss=None):
+    """DipRestoreMonitorDesc of monitor m (a RestorationFitMonitor or a GroupedRestorationFitMonitor) over these buffers:
+    `mask` is [mask_c][hw], out / img are planes of hw."""
+    return N.DipRestoreMonitorDesc(_ptr(out), _ptr(img), _ptr(mask), img.numel(), int(hw), int(mask_c), m.backtrack_db, _ptr(loss),
+                                   _ptr(partial), _ptr(records), m.capacity, m.show_every, 1 if m.backtracking else 0, 0,
+                                   _ptr(counter), _ptr(state))
+
+
+def restore_monitor_launches(lib, desc, params_ptr, n_arena, snapshot_ptr):
+    """dip_restore_monitor_dev and, with a snapshot arena, dip_arena_backtrack as (fn, args, name) triples."""
+    mon = [(lib.dip_restore_monitor_dev, (C.byref(desc),), "restore_monitor_dev")]
+    if snapshot_ptr is not None:
+        mon.append((lib.dip_arena_backtrack, (params_ptr, snapshot_ptr, n_arena, desc.state), "arena_backtrack"))
+    return mon
+
+
+def _mask4(mask, C_out, hw_shape, who):
+    """`mask` as a contiguous fp32 [1, 1|C_out, H, W] tensor: the rule of utils.loss_head.MSEHead(mask=)."""
+    m = mask.detach().float()
+    while m.dim() < 4:
+        m = m[None]
+    if m.shape[0] != 1 or m.shape[1] not in (1, C_out) or tuple(m.shape[2:]) != tuple(hw_shape):
+        raise ValueError(f"dip-amd: {who}: mask must be [1,1|{C_out},{hw_shape[0]},{hw_shape[1]}], got {tuple(m.shape)}")
+    return m.contiguous()
+
+
 class _DeviceRecords:
     """What FitMonitor and SRFitMonitor share: a [capacity, len(COLUMNS)] record table in device memory, the host's count `i`
     of recorded iterations, and the device counter the *_dev kernels index the table with (NativeIteration(monitor=))."""
@@ -113,6 +160,19 @@ class _DeviceRecords:
         # all issued work has run; update() passes `i` by value and leaves both alone, NativeIteration re-aligns them
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self._counter_host = 0
+
+    def _init_backtracking(self, net, backtracking):
+        """`engine` = the net's engine when the monitor back-tracks (it checkpoints the flat parameter arena), else None."""
+        self.engine = None
+        self.snapshot = None
+        if backtracking:
+            eng = getattr(net, "__dict__", {}).get("_dip_engine")
+            if eng is None:
+                raise RuntimeError("dip-amd: back-tracking needs a net built by models.skip.skip() (flat parameter arena)")
+            if getattr(eng, "kind", "skip") != "skip":
+                raise NotImplementedError(f"dip-amd: {type(self).__name__} back-tracking covers skip() nets only; construct it "
+                                          "with backtracking=False for a ResNet")
+            self.engine = eng
 
     def _sync_counter(self):
         """Sets the device counter to `i` on the current stream when it would not hold it (update() calls since the last
@@ -155,16 +215,7 @@ class FitMonitor(_DeviceRecords):
         self.state = torch.zeros(4, dtype=torch.float32, device=self.dev)
         self.partial = torch.empty(4 * self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float32, device=self.dev)
         self.out_avg = torch.zeros_like(self.noisy)
-        self.engine = None
-        self.snapshot = None
-        if backtracking:
-            eng = getattr(net, "__dict__", {}).get("_dip_engine")
-            if eng is None:
-                raise RuntimeError("dip-amd: back-tracking needs a net built by models.skip.skip() (flat parameter arena)")
-            if getattr(eng, "kind", "skip") != "skip":
-                raise NotImplementedError("dip-amd: FitMonitor back-tracking covers skip() nets only; construct it with "
-                                          "backtracking=False for a ResNet")
-            self.engine = eng
+        self._init_backtracking(net, backtracking)
 
     def update(self, out, loss=None):
         """Call once per closure evaluation, after backward() (like the reference, the fall-back
@@ -310,6 +361,94 @@ class SRFitMonitor(_DeviceRecords):
         return (self, self.records, self.partial, self.counter, self.img_LR, self.img_HR)
 
 
+class RestorationFitMonitor(_DeviceRecords):
+    """psrn_masked / psrn and the back-tracking of the restoration closure (restoration.ipynb:192-211) on the device: one record
+    per iteration, {loss, mse_masked, mse, psrn_masked, psrn, fell_back}, from the net output against `img` -- masked:
+    (out - img) * mask, the notebook's out * img_mask_np against img_masked -- and, when i % show_every == 0, the fall-back to
+    the last checkpoint when psrn_masked dropped by more than backtrack_db, or else the checkpoint.  No EMA: the closure has
+    none.  `mask` is [1, 1|C, H, W], as for utils.loss_head.MSEHead(mask=).  update() is the eager form (dip_restore_monitor +
+    dip_arena_backtrack); NativeIteration(monitor=this) issues dip_restore_monitor_dev, which reads the row index from
+    `counter`.  Back-tracking needs a skip() net (flat parameter arena); backtracking=False records only."""
+    COLUMNS = ("loss", "mse_masked", "mse", "psrn_masked", "psrn", "fell_back")
+    head_kind = None                                                # any head: the record needs the net output only
+    backtracking = property(lambda self: self.engine is not None)
+
+    def __init__(self, net, img, mask, show_every=50, backtrack_db=5.0, backtracking=True, capacity=16384):
+        # (what needs no GPU is refused first: the types and shapes, the settings, the net)
+        if not isinstance(img, torch.Tensor) or not isinstance(mask, torch.Tensor):
+            raise TypeError("dip-amd: RestorationFitMonitor: img and mask are tensors ([1,C,H,W] and [1,1|C,H,W])")
+        if img.dim() != 4 or img.shape[0] != 1:
+            raise ValueError(f"dip-amd: RestorationFitMonitor: img must be [1,C,H,W], got {tuple(img.shape)}")
+        mask = _mask4(mask, img.shape[1], img.shape[2:], "RestorationFitMonitor")
+        if int(show_every) <= 0 or int(capacity) <= 0:
+            raise ValueError("dip-amd: RestorationFitMonitor: show_every and capacity must be > 0")
+        self._init_backtracking(net, backtracking)
+        if not img.is_cuda:
+            raise RuntimeError("dip-amd: RestorationFitMonitor works on MI355X tensors only (no CPU fallback)")
+        self._init_records(img.device, capacity)
+        self.img = img.detach().contiguous().float()
+        self.mask, self.mask_c = mask.to(self.dev), int(mask.shape[1])
+        self.n, self.hw = self.img.numel(), int(img.shape[2] * img.shape[3])
+        self.show_every, self.backtrack_db = int(show_every), float(backtrack_db)
+        self.state = torch.zeros(4, dtype=torch.float32, device=self.dev)
+        self.partial = torch.empty(2 * self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float32, device=self.dev)
+
+    def update(self, out, loss=None):
+        """Call once per closure evaluation, after backward() (like the reference, the fall-back overwrites the parameters
+        AFTER the gradients of this iteration were computed)."""
+        if self.i >= self.capacity:
+            raise RuntimeError(f"dip-amd: RestorationFitMonitor capacity exceeded ({self.i} recorded, capacity {self.capacity}); "
+                               "construct it with capacity >= num_iter")
+        o = out.detach()
+        if o.shape != self.img.shape or not o.is_cuda or o.device != self.dev:
+            raise ValueError("dip-amd: RestorationFitMonitor.update: output shape/device does not match the image")
+        o = o.contiguous().float()
+        with torch.cuda.device(self.dev):        # raw HIP launches go to the current device's streams
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            lptr = None
+            if loss is not None:
+                self._loss = loss.detach().reshape(1).float()          # keep alive until the launch has run
+                lptr = self._loss.data_ptr()
+            check = 1 if (self.engine is not None and self.i % self.show_every == 0) else 0      # restoration.ipynb:198
+            N.check(self.lib.dip_restore_monitor(o.data_ptr(), self.img.data_ptr(), self.mask.data_ptr(), self.mask_c, self.n,
+                                                 self.hw, lptr, self.partial.data_ptr(), self.records[self.i].data_ptr(),
+                                                 self.state.data_ptr(), check, self.backtrack_db, stream), "restore_monitor")
+            snap = self._ensure_snapshot()
+            if snap is not None:
+                params = self.engine.params
+                N.check(self.lib.dip_arena_backtrack(params.data_ptr(), snap.data_ptr(), params.numel(),
+                                                     self.state.data_ptr(), stream), "arena_backtrack")
+        self._keep = o
+        self.i += 1
+
+    # ------------------------------------------------------------------ the device-indexed form (dip_optim.NativeIteration)
+    _ensure_snapshot = FitMonitor._ensure_snapshot
+
+    def _dev_descriptor(self, out):
+        """DipRestoreMonitorDesc over this monitor's buffers for the output buffer `out`; `loss` is filled in per iteration."""
+        return restore_monitor_descriptor(self, out, self.img, self.mask, self.mask_c, self.hw, self.partial, self.records,
+                                          self.counter, self.state)
+
+    def _plan(self, eng, out, head):
+        """(descriptor, launches) of an iteration that writes the net output to `out` (dip_optim.NativeIteration)."""
+        if tuple(self.img.shape) != tuple(out.shape):
+            raise ValueError(f"dip-amd: the RestorationFitMonitor's image is {tuple(self.img.shape)}, the net output is "
+                             f"{tuple(out.shape)}")
+        desc = self._dev_descriptor(out)
+        return desc, restore_monitor_launches(self.lib, desc, eng.params.data_ptr(), eng.params.numel(),
+                                              _ptr(self._ensure_snapshot()))
+
+    def _plan_key(self):
+        """What a compiled command array (dip_optim.NativeIteration) was built from: buffers by identity, settings by value."""
+        return (id(self), id(self.records), id(self.state), id(self.partial), id(self.snapshot), id(self.counter),
+                self.show_every, self.backtrack_db, id(self.img), id(self.mask), self.mask_c, id(self.engine), self.capacity,
+                self.n, self.hw)
+
+    def _plan_keep(self):
+        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
+        return (self, self.records, self.state, self.partial, self.snapshot, self.counter, self.img, self.mask, self.engine)
+
+
 class _GroupedRecords:
     """What GroupedFitMonitor and GroupedSRFitMonitor share: settings only, until a dip_group.GroupedFits adopts the monitor
     (once) and exposes the per-instance buffers of its slab rows here as [B, ...] views; `i` is the host's count of issued
@@ -385,6 +524,24 @@ class GroupedFitMonitor(_GroupedRecords):
     def _check_targets(self, targets):
         """imgs_gt against the group's targets: one [1,C,H,W] image per instance, shaped like the target."""
         self._check_images(self.imgs_gt, [t.shape for t in targets], "imgs_gt", "the target")
+
+
+class GroupedRestorationFitMonitor(_GroupedRecords):
+    """RestorationFitMonitor for the B fits of a dip_group.GroupedFits(masks=...): settings only.  The image and the mask are
+    the slab's own target and mask rows (no second copy); the group that adopts it places partial sums, records, state, counter
+    and -- with back-tracking -- the snapshot in its slab rows, behind everything a monitor-less masked group owns, and exposes
+    records [B, capacity, 6], state [B, 4] (writable), counter [B] int32 and snapshot [B, n_arena] (None without back-tracking)
+    here.  ONE dip_restore_monitor_dev and ONE dip_arena_backtrack call inside the group bracket serve all B, and every
+    instance takes its own decision."""
+    COLUMNS = RestorationFitMonitor.COLUMNS
+
+    def __init__(self, show_every=50, backtrack_db=5.0, backtracking=True, capacity=16384):
+        self.show_every, self.backtrack_db = int(show_every), float(backtrack_db)
+        self.backtracking = bool(backtracking)
+        self._init_group(capacity)
+        if self.show_every <= 0 or self.capacity <= 0:
+            raise ValueError("dip-amd: GroupedRestorationFitMonitor: show_every and capacity must be > 0")
+        self.state = self.snapshot = None
 
 
 class GroupedSRFitMonitor(_GroupedRecords):

@@ -706,9 +706,9 @@ int dip_fit_monitor(const float* out, const float* noisy, const float* gt, float
                     float exp_weight, int first, const float* loss, float* partial, float* record,
                     float* state, int check_backtrack, float backtrack_db, void* stream);
 /* dip_fit_monitor with the iteration index in DEVICE memory: the same bookkeeping of the reference closure
- * (denoising.ipynb:214-248; restoration.ipynb:192-211) in a form whose launch arguments do not change from one iteration
- * to the next, so it can be a command of dip_iter_run's lists (a descriptor pointer plus the stream, like
- * dip_loss_head_fwd).  With i = counter[0]:
+ * (denoising.ipynb:214-248; restoration.ipynb:192-211 is dip_restore_monitor / dip_restore_monitor_dev below) in a form whose
+ * launch arguments do not change from one iteration to the next, so it can be a command of dip_iter_run's lists (a descriptor
+ * pointer plus the stream, like dip_loss_head_fwd).  With i = counter[0]:
  *   first           = (i == 0)                                 (:214 `if out_avg is None`)
  *   check_backtrack = backtracking && (i % show_every != 0)    (:238 `if i % show_every:`)
  *   record          = records + 8*i
@@ -785,6 +785,58 @@ typedef struct DipSRMonitorDesc {
 int dip_sr_monitor(const float* out_HR, const float* out_LR, const float* img_HR, const float* img_LR, int64_t n_hr,
                    int64_t n_lr, const float* loss, float* partial, float* record, void* stream);
 int dip_sr_monitor_dev(const DipSRMonitorDesc* d, void* stream);
+
+/* The bookkeeping of the restoration / inpainting closure (restoration.ipynb:180-219) without host round trips: after
+ * backward() the notebook does, in every iteration,
+ *   psrn_masked = compare_psnr(img_masked, out.detach().cpu().numpy()[0] * img_mask_np)            (restoration.ipynb:192)
+ *   psrn        = compare_psnr(img_np,     out.detach().cpu().numpy()[0])                          (restoration.ipynb:193)
+ * -- two device-to-host copies and two synchronisations -- and, when i % show_every == 0 (restoration.ipynb:198), falls back
+ * to the last parameter checkpoint when psrn_masked dropped by more than 5 dB (restoration.ipynb:202-208) or else copies
+ * every parameter to the CPU and remembers psrn_masked (restoration.ipynb:209-211).  Here one streaming pass over the NCHW
+ * output (n elements, planes of hw) leaves per block the fp32 sums of ((out - img) * m)^2 and (out - img)^2, with
+ * m = mask[mask_c == 1 ? i % hw : i] (img_masked = img * mask) -- per thread two fmaf chains over a grid-stride walk, per
+ * block a 256-wide LDS tree in a fixed pairing order -- and a one-block kernel sums them in double, in block order:
+ *   record <- {loss, mse_masked, mse, psnr_masked, psnr, fell_back}     (6 floats; mse = sum / n, psnr = -10 log10(mse), data
+ *              range 1: compare_psnr over the whole array, as the notebook calls it; `loss` is a device scalar or NULL (0))
+ *   state   =  {psnr_masked_last, restore, have_last, snapshot}: the float[4] of dip_fit_monitor, so dip_arena_backtrack
+ *              applies the decision unchanged; zero it before the first call.  With check_backtrack != 0: restore = 1 when
+ *              have_last is set and psnr_masked - psnr_masked_last < -backtrack_db, otherwise snapshot = 1,
+ *              psnr_masked_last <- psnr_masked and have_last <- 1.  (The notebook starts psrn_masked_last at 0 and has no
+ *              have_last; for images and outputs in [0, 1] psnr_masked >= 0, so the two rules decide identically.)
+ * Deterministic, no float atomics, no EMA (this closure has none).  `partial` is scratch of 2*dip_fit_monitor_nblk(n) floats.
+ * dip_restore_monitor: `record` is the row and check_backtrack the host's `i % show_every == 0`, by value (the eager
+ * closure's update()).
+ * dip_restore_monitor_dev: the iteration index i = counter[0] lives in DEVICE memory, so the arguments do not change between
+ * iterations and the call can be a command of dip_iter_run's lists: check_backtrack = backtracking && (i % show_every == 0),
+ * the row is records + 6*i, and the last store is counter[0] <- i + 1.  i outside [0, capacity): records and counter are left
+ * alone and state[1] = state[3] = 0, so the dip_arena_backtrack behind it does nothing (the guard of dip_fit_monitor_dev;
+ * callers check the capacity first).  The descriptor is read when the call launches: `loss` may be rewritten by the host
+ * between calls.
+ * loss may be NULL; every other pointer is required; n, hw, capacity, show_every > 0, n % hw == 0 and mask_c is 1 or n / hw,
+ * otherwise -1 before anything is launched.  sizeof(DipRestoreMonitorDesc) == 104 (LP64).
+ * Inside dip_group_begin / dip_group_end both calls serve the B monitors of the group with two dispatches (family
+ * DIP_FAM_LOSS; a workgroup belongs to one instance): every non-NULL pointer must lie in instance 0's slab, and instance b
+ * works on the same fields advanced by b * stride -- its own counter, partial sums, record row, state and decision. */
+typedef struct DipRestoreMonitorDesc {
+    const float* out;       /* [n] the network output of this iteration, NCHW */
+    const float* img;       /* [n] the image the loss fits (restoration.ipynb: img_var) */
+    const float* mask;      /* [mask_c][hw] */
+    int64_t n, hw;
+    int mask_c;             /* 1 or n / hw */
+    float backtrack_db;
+    const float* loss;      /* 1 float or NULL: column 0 of the record */
+    float* partial;         /* 2*dip_fit_monitor_nblk(n) floats of scratch */
+    float* records;         /* [capacity][6] */
+    int capacity, show_every;
+    int backtracking;       /* 0 / 1 */
+    int reserved;
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    float* state;           /* float[4], as for dip_fit_monitor */
+} DipRestoreMonitorDesc;
+int dip_restore_monitor(const float* out, const float* img, const float* mask, int mask_c, int64_t n, int64_t hw,
+                        const float* loss, float* partial, float* record, float* state, int check_backtrack,
+                        float backtrack_db, void* stream);
+int dip_restore_monitor_dev(const DipRestoreMonitorDesc* d, void* stream);
 
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
