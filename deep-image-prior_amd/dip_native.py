@@ -141,6 +141,13 @@ class DipRestoreMonitorDesc(C.Structure):
                 ("reserved", C.c_int32), ("counter", C.c_void_p), ("state", C.c_void_p)]
 
 
+class DipEarlyStopDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("ring", C.c_void_p), ("mean", C.c_void_p), ("partial", C.c_void_p),
+                ("records", C.c_void_p), ("state", C.c_void_p), ("counter", C.c_void_p), ("best_out", C.c_void_p),
+                ("n", C.c_int64), ("window", C.c_int32), ("patience", C.c_int32), ("capacity", C.c_int32),
+                ("loss", C.c_void_p)]
+
+
 _SIGS = {
     "dip_abi_version": (C.c_int, []),
     "dip_build_id": (C.c_char_p, []),
@@ -291,6 +298,8 @@ _SIGS = {
     "dip_restore_monitor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "dip_restore_monitor_dev": (C.c_int, [C.POINTER(DipRestoreMonitorDesc), C.c_void_p]),
+    "dip_early_stop_dev": (C.c_int, [C.POINTER(DipEarlyStopDesc), C.c_void_p]),
+    "dip_early_stop_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),
     "dip_lanczos_down_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

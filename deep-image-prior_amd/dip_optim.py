@@ -366,9 +366,22 @@ class NativeIteration:
         it.run(num_iter); monitor.history()           # [iters, 6]: loss, mse_masked, mse, psrn_masked, psrn, fell_back
 
     step() / run(n) past the monitor's capacity raise before anything is issued.  The monitor's buffers and settings are
-    part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt)."""
+    part of the plan's key (replace `monitor.out_avg`, or assign another monitor to `it.monitor`: the arrays are rebuilt).
 
-    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None):
+    early_stop=EarlyStopMonitor(img_like, window, patience, net=net) is independent of monitor=: the ground-truth-free stopping
+    criterion (the windowed moving variance of the output; utils.fit_monitor) as one more command array on the main stream,
+    behind the monitor's array if there is one and in front of Adam -- where `es.update(out)` stands in the eager closure, so
+    `es.best_params` are the parameters that produced `es.best_out`.  It holds dip_early_stop_dev (which reads the row index
+    from `es.counter` and the ring head from `es.state`) and, with net=, dip_early_stop_keep over the parameter arena.  It
+    does not touch the fit: losses and parameters are bit-identical to early_stop=None, and with early_stop=None the plan's key
+    is what it was.  Eager `es.update(out)` calls and native iterations alternate on one monitor.
+
+        es = EarlyStopMonitor(img_noisy, window=100, patience=1000, net=net, capacity=num_iter)
+        it = NativeIteration(net, head, opt, net_input, reg_noise=reg, early_stop=es)
+        issued, losses = it.run_until(num_iter, check_every=50)      # polls the 4-byte `stopped` word once per 50 iterations
+        es.best_iter, es.best_out; es.restore_best()"""
+
+    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None, early_stop=None):
         import dip_group
         from utils.loss_head import MSEHead, SRHead
         from utils.reg_noise import RegNoise
@@ -391,7 +404,9 @@ class NativeIteration:
                              "opt_over with 'input' or 'down' goes through the eager closure")
         # (the monitor's type is refused before the first check that needs a GPU)
         self.monitor, self.device = monitor, getattr(net_input, "device", None)
+        self.early_stop = early_stop
         self._check_monitor()
+        self._check_early_stop()
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
                                "fallback)")
@@ -449,23 +464,39 @@ class NativeIteration:
         if m.engine is not None and m.engine is not self.engine:
             raise ValueError(f"dip-amd: the {type(m).__name__} back-tracks another net (it was built for a different skip() net)")
 
+    def _check_early_stop(self):
+        """What can be said about `early_stop` before the output size is known (the image shape: _build)."""
+        from utils.fit_monitor import EarlyStopMonitor
+        es = self.early_stop
+        if es is None:
+            return
+        if not isinstance(es, EarlyStopMonitor):
+            raise TypeError(f"dip-amd: early_stop must be a utils.fit_monitor.EarlyStopMonitor or None, got {type(es).__name__}")
+        if es.dev != self.device:
+            raise RuntimeError(f"dip-amd: the EarlyStopMonitor lives on {es.dev}, the iteration runs on {self.device}")
+        if es.engine is not None and es.engine is not self.engine:
+            raise ValueError("dip-amd: the EarlyStopMonitor keeps the parameters of another net (it was built with a different "
+                             "skip() net)")
+
     # -------------------------------------------------------------------------------------------- the command arrays
     def _signature(self, sig):
         """Everything a slot of the command arrays was computed from.  Objects by identity: the arrays hold raw pointers, and
         the plan keeps every object of its key alive, so neither an id nor an address can be recycled unnoticed."""
-        eng, head, opt, reg, m = self.engine, self.head, self.opt, self.reg, self.monitor
+        eng, head, opt, reg, m, es = self.engine, self.head, self.opt, self.reg, self.monitor, self.early_stop
         # (an engine that has never planned has no op lists yet: None never equals a built key)
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
                 opt.lr, opt.betas, opt.eps, id(opt._groups),
                 head._plan_key(),
                 None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
-            + (() if m is None else (m._plan_key(),))          # (monitor=None: the key as it was)
+            + (() if m is None else (m._plan_key(),)) \
+            + (() if es is None else (("early_stop", es._plan_key()),))          # (None: the key as it was)
 
     def _build(self):
-        eng, head, opt, reg, m = self.engine, self.head, self.opt, self.reg, self.monitor
+        eng, head, opt, reg, m, es = self.engine, self.head, self.opt, self.reg, self.monitor, self.early_stop
         lib = N.lib()
         dev = self.device
         self._check_monitor()
+        self._check_early_stop()
         noisy = reg is not None and reg.std > 0
         x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
         _, Cimg, H, W = x.shape
@@ -507,15 +538,21 @@ class NativeIteration:
             mdesc, mon = m._plan(eng, out, head)
             mdesc.loss = loss0.data_ptr()
             phases.insert(4, on_main(mon))
+        edesc = None
+        if es is not None:
+            # es.update(out)'s place: behind the monitor (a fall-back has been applied), in front of Adam -- the arena it keeps
+            # holds the parameters that produced `out`
+            edesc, stop = es._plan(eng, out, head)
+            phases.insert(len(phases) - 1, on_main(stop))
         lists = N.IterList(phases)
         views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]
         self.out = out
         # everything a slot points to stays alive with the plan, and so does every object whose id is part of the key
-        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, views=views, x=x, state=st, loss0=loss0,
+        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, edesc=edesc, views=views, x=x, state=st, loss0=loss0,
                           keep=(head._plan_keep(), eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
                                 None if reg is None else (reg.saved, reg.out, reg.offset),
-                                None if m is None else m._plan_keep()))
+                                None if m is None else m._plan_keep(), None if es is None else es._plan_keep()))
         self._key = self._signature(opt._sig)
 
     # -------------------------------------------------------------------------------------------- run
@@ -523,16 +560,23 @@ class NativeIteration:
         self._check_training()
         self._check_capture()
         self._check_monitor()                     # (`it.monitor` may have been replaced)
+        self._check_early_stop()
         self.head._check_state()                  # (an SRHead's down-sampler may have become trainable)
         m = self.monitor
         if m is not None and m.i + n > m.capacity:
             raise RuntimeError(f"dip-amd: {type(m).__name__} capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
+                               "construct it with capacity >= num_iter")
+        es = self.early_stop
+        if es is not None and es.i + n > es.capacity:
+            raise RuntimeError(f"dip-amd: EarlyStopMonitor capacity exceeded ({es.i} recorded + {n} > capacity {es.capacity}); "
                                "construct it with capacity >= num_iter")
         # (the parameters' addresses are part of the key: they also say that the engine's arena still holds the parameters)
         if self._signature(self.opt._signature()) != self._key:
             self._build()
         if m is not None:
             m._sync_counter()                     # eager update() calls in between: the device index follows monitor.i
+        if es is not None:
+            es._sync_counter()
         eng = self.engine
         ptrs = [torch.cuda.current_stream(self.device).cuda_stream]
         if eng.two_streams:
@@ -556,6 +600,8 @@ class NativeIteration:
         self.iterations += n
         if self.monitor is not None:
             self.monitor._advance(n)
+        if self.early_stop is not None:
+            self.early_stop._advance(n)
 
     @torch.no_grad()
     def step(self):
@@ -586,6 +632,32 @@ class NativeIteration:
                 if done:
                     self._finish(done)
         return losses
+
+    def run_until(self, max_iter, check_every=50):
+        """Runs until the EarlyStopMonitor says stop, or max_iter: issues `check_every` iterations at a time and reads the
+        device's 4-byte `stopped` word after each batch (one copy and one synchronisation per batch).  Returns
+        (iterations_issued, losses [iterations_issued], a device tensor).  It stops at the first batch boundary at or after the
+        stopping iteration: at most check_every - 1 iterations too many, which keep training the net but cannot touch the
+        frozen best_out / best_params (es.restore_best() puts the minimum's parameters back)."""
+        es = self.early_stop
+        if es is None:
+            raise RuntimeError("dip-amd: NativeIteration.run_until needs early_stop=EarlyStopMonitor(...)")
+        max_iter, check_every = max(int(max_iter), 0), int(check_every)
+        if check_every < 1:
+            raise ValueError(f"dip-amd: run_until: check_every must be >= 1, got {check_every}")
+        if es.i + max_iter > es.capacity:          # (before anything is issued, as run(max_iter) would)
+            raise RuntimeError(f"dip-amd: EarlyStopMonitor capacity exceeded ({es.i} recorded + {max_iter} > capacity "
+                               f"{es.capacity}); construct it with capacity >= num_iter")
+        parts, issued = [], 0
+        while issued < max_iter:
+            n = min(check_every, max_iter - issued)
+            parts.append(self.run(n))
+            issued += n
+            if es.stopped:
+                break
+        with torch.cuda.device(self.device):
+            losses = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=self.device)
+        return issued, losses
 
 
 class ArenaLBFGS:

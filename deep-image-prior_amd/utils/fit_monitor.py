@@ -76,6 +76,24 @@ finalize, then dip_arena_backtrack; columns loss, mse_masked, mse, psrn_masked, 
     mon = GroupedRestorationFitMonitor(show_every=50, capacity=num_iter)            # B fits: settings only, adopted once
     g = GroupedFits(nets, net_inputs, imgs, masks=masks, monitor=mon)               # ONE dip_restore_monitor_dev and ONE
     g.capture(); g.run(num_iter - 3); mon.history()                                 # dip_arena_backtrack call; [B, iters, 6]
+
+None of the notebooks decides WHEN to stop: num_iter is picked by hand and a person looks at the plot.  EarlyStopMonitor is the
+ground-truth-free criterion for an unattended fit -- the windowed moving variance of the output (ES-WMV, Wang et al., "Early
+Stopping for Deep Image Prior"): stop after `patience` iterations without a new minimum of the variance over the last `window`
+outputs, keep the output (and, with net=, the parameters) of the minimum.  On the host that is an `out.detach().cpu()` and a
+synchronisation per iteration; here the window is a ring in device memory (dip_early_stop_dev: one streaming pass, a one-block
+finalize, a conditional copy; columns var, var_min, best_iter, wait, stopped), and the host polls a 4-byte flag:
+
+    es = EarlyStopMonitor(img_noisy_torch, window=100, patience=1000, net=net, capacity=num_iter)
+    def closure():
+        total_loss, out = head(net_input)
+        total_loss.backward()
+        es.update(out)                                       # no host sync; after backward(), before the optimiser's step
+        return total_loss
+
+    it = NativeIteration(net, head, opt, net_input, reg_noise=reg, early_stop=es)   # next to monitor=, independent of it
+    issued, losses = it.run_until(num_iter, check_every=50)                         # one 4-byte read per 50 iterations
+    es.best_iter, es.best_out; es.restore_best()                                    # the net carries the minimum's parameters
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
 """
@@ -447,6 +465,167 @@ class RestorationFitMonitor(_DeviceRecords):
     def _plan_keep(self):
         """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
         return (self, self.records, self.state, self.partial, self.snapshot, self.counter, self.img, self.mask, self.engine)
+
+
+def early_stop_state(dev):
+    """The 64-byte state of dip_early_stop_dev before the first iteration, as int32[16]: var_min = var = +inf (double[1],
+    double[2]), best_iter = -1 (int32[9]), everything else zero."""
+    st = torch.zeros(16, dtype=torch.int32, device=dev)
+    st.view(torch.float64)[1:3] = float("inf")
+    st[9] = -1
+    return st
+
+
+def early_stop_descriptor(m, out, ring, mean, partial, records, state, counter, best_out, loss=None):
+    """DipEarlyStopDesc of monitor m (window, patience, capacity) over these buffers."""
+    return N.DipEarlyStopDesc(_ptr(out), _ptr(ring), _ptr(mean), _ptr(partial), _ptr(records), _ptr(state), _ptr(counter),
+                              _ptr(best_out), out.numel(), m.window, m.patience, m.capacity, _ptr(loss))
+
+
+def early_stop_launches(lib, desc, params_ptr, n_arena, best_params_ptr):
+    """dip_early_stop_dev and, with a best_params arena, dip_early_stop_keep as (fn, args, name) triples."""
+    es = [(lib.dip_early_stop_dev, (C.byref(desc),), "early_stop_dev")]
+    if best_params_ptr is not None:
+        es.append((lib.dip_early_stop_keep, (params_ptr, best_params_ptr, n_arena, desc.state), "early_stop_keep"))
+    return es
+
+
+class EarlyStopMonitor(_DeviceRecords):
+    """When to stop, without a ground truth: the windowed moving variance of the net output (ES-WMV; Wang et al., "Early
+    Stopping for Deep Image Prior") on the device.  The variance over the last `window` outputs falls while the fit converges on
+    the image and rises again once it fits the noise; the fit counts as done after `patience` iterations without a new minimum,
+    and the output at the minimum is kept in `best_out`.  One record per iteration, {var, var_min, best_iter, wait, stopped};
+    the first window - 1 rows are {inf, inf, -1, 0, 0}, the rows after the stopping iteration repeat its row.  Once stopped,
+    the window, var_min, best_iter, best_out and best_params are frozen.  A NaN output makes the variance NaN: no minimum is
+    taken and `wait` advances (the fp64 running mean keeps the NaN, so the monitor then stops after `patience` iterations).
+
+    `img_like` gives the shape [1,C,H,W] and the device of the output.  net= a skip() net: the flat parameter arena at the
+    minimum is kept too (`best_params`; restore_best() copies it back); without it only best_out is kept.  update(out) is the
+    eager form, NativeIteration(early_stop=this) issues the same entry point (dip_early_stop_dev reads the row index from
+    `counter`, the ring head and the fill count from `state`), and the two may alternate.
+
+    Memory: the ring holds `window` outputs, 4 * window * n bytes -- 315 MB for window = 100 at 3 x 512 x 512 -- plus 8 n bytes
+    of fp64 mean and 4 n of best_out (`memory_bytes`)."""
+    COLUMNS = ("var", "var_min", "best_iter", "wait", "stopped")
+    head_kind = None                                                # any head: the record needs the net output only
+
+    def __init__(self, img_like, window=100, patience=1000, net=None, capacity=16384):
+        # (what needs no GPU is refused first: the settings, the net)
+        if not isinstance(img_like, torch.Tensor):
+            raise TypeError("dip-amd: EarlyStopMonitor: img_like is a tensor shaped like the net output ([1,C,H,W])")
+        if int(window) < 2:
+            raise ValueError(f"dip-amd: EarlyStopMonitor: window must be >= 2, got {window}")
+        if int(patience) < 1:
+            raise ValueError(f"dip-amd: EarlyStopMonitor: patience must be >= 1, got {patience}")
+        if int(capacity) < 1 or int(capacity) > 2 ** 24:
+            raise ValueError(f"dip-amd: EarlyStopMonitor: capacity must be in [1, 2**24] (best_iter is a float32 column), got "
+                             f"{capacity}")
+        self._init_backtracking(net, net is not None)               # `engine`: the net's, or None without net=
+        if not img_like.is_cuda:
+            raise RuntimeError("dip-amd: EarlyStopMonitor works on MI355X tensors only (no CPU fallback)")
+        self._init_records(img_like.device, capacity)
+        self.window, self.patience = int(window), int(patience)
+        self.shape, self.n = tuple(img_like.shape), img_like.numel()
+        if self.n < 1:
+            raise ValueError("dip-amd: EarlyStopMonitor: img_like is empty")
+        self.ring = torch.empty((self.window, self.n), dtype=torch.float32, device=self.dev)
+        self.mean = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+        self.partial = torch.empty(self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float64, device=self.dev)
+        self.state = early_stop_state(self.dev)
+        self.best_out = torch.zeros(self.shape, dtype=torch.float32, device=self.dev)
+        self.best_params = None
+
+    @property
+    def memory_bytes(self):
+        """Device memory this monitor holds (the ring dominates: 4 * window * n)."""
+        ts = (self.ring, self.mean, self.partial, self.state, self.best_out, self.records, self.counter, self.best_params)
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+    @property
+    def best_iter(self):
+        """The iteration of the minimum, -1 before the first decision (reads one value; synchronises)."""
+        return int(self.state[9].item())
+
+    @property
+    def stopped(self):
+        """1 once `patience` iterations passed without a new minimum (reads one value; synchronises)."""
+        return int(self.state[10].item())
+
+    def _ensure_best_params(self):
+        """The arena kept at the minimum, as large as the engine's parameter arena and on its device (None without net=)."""
+        if self.engine is None:
+            return None
+        params = self.engine.params
+        if self.best_params is None or self.best_params.numel() != params.numel() or self.best_params.device != params.device:
+            self.best_params = torch.zeros_like(params)
+        return self.best_params
+
+    def restore_best(self):
+        """Copies best_params back into the net's parameter arena: the net then produces best_out again."""
+        if self.engine is None:
+            raise RuntimeError("dip-amd: EarlyStopMonitor.restore_best needs net= (the monitor keeps best_out only)")
+        if self.best_params is None or self.best_iter < 0:
+            raise RuntimeError("dip-amd: EarlyStopMonitor.restore_best: no minimum has been recorded yet")
+        params = self.engine.params
+        if params.numel() != self.best_params.numel() or params.device != self.best_params.device:
+            raise RuntimeError("dip-amd: EarlyStopMonitor.restore_best: the net's parameter arena changed since the minimum")
+        with torch.no_grad():
+            params.copy_(self.best_params)
+
+    def _check_out(self, shape, who):
+        if tuple(shape) != self.shape:
+            raise ValueError(f"dip-amd: {who}: the EarlyStopMonitor was built for {self.shape}, the net output is {tuple(shape)}")
+
+    def update(self, out):
+        """Call once per closure evaluation, after backward() and before the optimiser's step: best_params are then the
+        parameters that produced best_out."""
+        if self.i >= self.capacity:
+            raise RuntimeError(f"dip-amd: EarlyStopMonitor capacity exceeded ({self.i} recorded, capacity {self.capacity}); "
+                               "construct it with capacity >= num_iter")
+        o = out.detach()
+        self._check_out(o.shape, "EarlyStopMonitor.update")
+        if not o.is_cuda or o.device != self.dev:
+            raise ValueError(f"dip-amd: EarlyStopMonitor.update: the output is on {o.device}, the monitor lives on {self.dev} "
+                             "(no CPU fallback)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dip-amd: EarlyStopMonitor.update cannot be captured into a hipGraph (the row index is "
+                               "host-synchronised state)")
+        o = o.contiguous().float()
+        with torch.cuda.device(self.dev):        # raw HIP launches go to the current device's streams
+            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            self._sync_counter()
+            desc = self._dev_descriptor(o)
+            N.check(self.lib.dip_early_stop_dev(C.byref(desc), stream), "early_stop_dev")
+            best = self._ensure_best_params()
+            if best is not None:
+                params = self.engine.params
+                N.check(self.lib.dip_early_stop_keep(params.data_ptr(), best.data_ptr(), params.numel(),
+                                                     self.state.data_ptr(), stream), "early_stop_keep")
+        self._keep = o
+        self._advance(1)
+
+    # ------------------------------------------------------------------ the form inside dip_optim.NativeIteration(early_stop=)
+    def _dev_descriptor(self, out):
+        """DipEarlyStopDesc over this monitor's buffers for the output buffer `out`."""
+        return early_stop_descriptor(self, out, self.ring, self.mean, self.partial, self.records, self.state, self.counter,
+                                     self.best_out)
+
+    def _plan(self, eng, out, head):
+        """(descriptor, launches) of an iteration that writes the net output to `out` (dip_optim.NativeIteration)."""
+        self._check_out(out.shape, "NativeIteration")
+        desc = self._dev_descriptor(out)
+        return desc, early_stop_launches(self.lib, desc, eng.params.data_ptr(), eng.params.numel(),
+                                         _ptr(self._ensure_best_params()))
+
+    def _plan_key(self):
+        """What a compiled command array (dip_optim.NativeIteration) was built from: buffers by identity, settings by value."""
+        return (id(self), id(self.records), id(self.state), id(self.ring), id(self.mean), id(self.partial), id(self.best_out),
+                id(self.best_params), id(self.counter), self.window, self.patience, id(self.engine), self.capacity, self.n)
+
+    def _plan_keep(self):
+        """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
+        return (self, self.records, self.state, self.ring, self.mean, self.partial, self.best_out, self.best_params,
+                self.counter, self.engine)
 
 
 class _GroupedRecords:

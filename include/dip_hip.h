@@ -838,6 +838,56 @@ int dip_restore_monitor(const float* out, const float* img, const float* mask, i
                         float backtrack_db, void* stream);
 int dip_restore_monitor_dev(const DipRestoreMonitorDesc* d, void* stream);
 
+/* Ground-truth-free early stopping: the windowed moving variance of the net output (ES-WMV; Wang et al., "Early Stopping for
+ * Deep Image Prior").  What it replaces is the host loop's per-iteration `out.detach().cpu()` -- one device-to-host copy of
+ * the output and one synchronisation per iteration, then a variance over the last W outputs on the host; the reference itself
+ * stops by a hand-picked num_iter (utils/common_utils.py:223-230 runs exactly num_iter iterations).
+ * With outputs x_0, x_1, ... of n floats, window W >= 2 and patience P >= 1, for iteration t = counter[0], while not stopped:
+ *   t <  W-1: x_t enters the window, no decision;
+ *   t >= W-1: mu_t = mean of x_{t-W+1..t};  var_t = sum_w |x_{t-w} - mu_t|^2 / (W n);
+ *             var_t < var_min (strict): var_min <- var_t, best_iter <- t, wait <- 0, best_out <- x_t, improved <- 1
+ *             otherwise:                wait <- wait + 1;  wait >= P: stopped <- 1
+ * Once stopped, ring, mean, M2, var_min, best_iter and best_out are frozen; later calls only write their record row (the
+ * stopping iteration's row again) and advance the counter.  A NaN output makes var_t NaN: the comparison is false and wait
+ * advances (no special case; the fp64 mean keeps the NaN, so the fit then stops after P iterations).
+ *   record <- {var, var_min, best_iter, wait, stopped}     (5 floats per row; warm-up rows are {inf, inf, -1, 0, 0};
+ *              best_iter is exact in fp32 up to 2^24)
+ * Arithmetic: a ring [W][n] of fp32 outputs, a per-element fp64 mean and a scalar fp64 M2, updated in ONE streaming pass
+ * (256 threads, grid-stride, dip_fit_monitor_nblk(n) blocks; 28 n bytes of traffic) --
+ *   warm-up, k-th sample:   d = x_new - mu;  mu' = mu + d/k;  M2 += d (x_new - mu')                      (Welford)
+ *   window full:            d = x_new - x_old;  mu' = mu + d/W;  M2 += d ((x_new - mu') + (x_old - mu))
+ * -- with one fp64 partial per block from a 256-wide LDS tree in a fixed pairing order; a one-block kernel sums the partials
+ * in a fixed order (64 lanes, each a contiguous run of blocks in block order, then the lane sums in lane order), takes the decision on the fp64 var = M2 / (W n), rounds it once to fp32 for the record and advances
+ * counter[0]; a conditional copy then keeps out in best_out.  Deterministic, no float atomics, nothing synchronises.
+ * state (64 bytes, 8-byte aligned), two views of one buffer:
+ *   double[0] M2, double[1] var_min, double[2] the latest var;
+ *   int32[6] ring head, [7] fill count, [8] wait, [9] best_iter, [10] stopped, [11] improved (this call found a new minimum).
+ *   Before the first call: all zero except var_min = var = +inf and best_iter = -1.
+ * t outside [0, capacity): nothing but improved <- 0 is written (the guard of dip_restore_monitor_dev; callers check the
+ * capacity first).  `loss` is not part of the record and is not read; the field keeps the descriptor in the shape of the other
+ * monitors' (dip_optim.NativeIteration rewrites it per iteration).  Every other pointer is required; n, window, patience,
+ * capacity > 0 and window >= 2, otherwise -1 before anything is launched.  sizeof(DipEarlyStopDesc) == 96 (LP64).
+ * The kernels have grouped instantiations (family DIP_FAM_LOSS: every non-NULL pointer in instance 0's slab, instance b works
+ * on the same fields advanced by b * stride); GroupedFits does not use them yet.
+ * dip_early_stop_keep: dst <- src (n floats, any n, any 4-byte alignment; whole quads only where both are 16-byte aligned)
+ * when state's `improved` is set, else nothing: issued behind dip_early_stop_dev over the flat parameter arena, it keeps the
+ * parameters that produced best_out. */
+typedef struct DipEarlyStopDesc {
+    const float* out;       /* [n] the network output of this iteration */
+    float* ring;            /* [window][n] the last `window` outputs */
+    double* mean;           /* [n] fp64 mean over the window */
+    double* partial;        /* dip_fit_monitor_nblk(n) doubles of scratch */
+    float* records;         /* [capacity][5] */
+    void* state;            /* 64 bytes, see above */
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    float* best_out;        /* [n] the output at the minimum */
+    int64_t n;
+    int window, patience, capacity;
+    const float* loss;      /* not read */
+} DipEarlyStopDesc;
+int dip_early_stop_dev(const DipEarlyStopDesc* d, void* stream);
+int dip_early_stop_keep(const float* src, float* dst, int64_t n, const void* state, void* stream);
+
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
  * k x k stride-`factor` correlation with the fixed taps; NCHW [C][H][W] -> [C][H/f][W/f]. */
