@@ -209,7 +209,9 @@ __global__ __launch_bounds__(256) void noise_axpy_kernel(const float* __restrict
     float nrm[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1)
+        // (0,1]: 2^-25 for word >> 8 == 0; from 2^23 up the + 0.5f ties to even, and 2^24 - 1 gives exactly 1.0 (radius 0).
+        // DESIGN.md "The reg-noise stream" is the specification; tests/noise_ref.py restates it in numpy.
+        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
         const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
         const float rad = sqrtf(-2.0f * __logf(u1));
         float s, co;
@@ -458,6 +460,7 @@ extern "C" int dip_adam_step_dev(float* p, const float* g, float* m, float* v, i
 extern "C" int dip_noise_axpy(const float* z, float* out, int64_t n, float sigma, uint64_t seed, uint64_t offset,
                               void* stream) {
     if (n <= 0) return 0;
+    if (z == nullptr || out == nullptr) DIP_FAIL("noise_axpy: z or out is NULL");
     const int64_t quads = (n + 3) / 4;
     dip_launch_pair<DIP_FAM_LOSS>(noise_axpy_kernel<false>, noise_axpy_kernel<true>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
                                   (hipStream_t)stream, z, out, n, sigma, seed, offset, (const uint64_t*)nullptr);
@@ -471,6 +474,7 @@ extern "C" int dip_noise_axpy_dev(const float* z, float* out, int64_t n, float s
                                   uint64_t* offset_dev, void* stream) {
     if (n <= 0) return 0;
     if (offset_dev == nullptr) DIP_FAIL("noise_axpy_dev: offset pointer is NULL");
+    if (z == nullptr || out == nullptr) DIP_FAIL("noise_axpy_dev: z or out is NULL");
     const int64_t quads = (n + 3) / 4;
     dip_launch_pair<DIP_FAM_LOSS>(noise_axpy_kernel<false>, noise_axpy_kernel<true>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
                                   (hipStream_t)stream, z, out, n, sigma, seed, (uint64_t)0, (const uint64_t*)offset_dev);
@@ -483,6 +487,7 @@ extern "C" int dip_noise_axpy_dev(const float* z, float* out, int64_t n, float s
 extern "C" int dip_noise_axpy_dev2(const float* z, float* out, int64_t n, float sigma, uint64_t* state_dev, void* stream) {
     if (n <= 0) return 0;
     if (state_dev == nullptr) DIP_FAIL("noise_axpy_dev2: state pointer is NULL");
+    if (z == nullptr || out == nullptr) DIP_FAIL("noise_axpy_dev2: z or out is NULL");
     const int64_t quads = (n + 3) / 4;
     dip_launch_pair<DIP_FAM_LOSS>(noise_axpy_kernel<false, true>, noise_axpy_kernel<true, true>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0,
                                   (hipStream_t)stream, z, out, n, sigma, (uint64_t)0, (uint64_t)0, (const uint64_t*)state_dev);

@@ -561,7 +561,9 @@ int dip_adam_step(float* p, const float* g, float* m, float* v, int64_t n, doubl
                   double beta2, double eps, int step, void* stream);
 
 /* net_input = z + sigma * N(0,1): the closure's reg-noise line (denoising.ipynb:208-209),
- * counter-based Philox4x32-10 + Box-Muller, NCHW in / NCHW out (elementwise). */
+ * counter-based Philox4x32-10 + Box-Muller, NCHW in / NCHW out (elementwise).  The stream is specified in DESIGN.md
+ * ("The reg-noise stream").  All three entry points: n <= 0 returns 0 and launches nothing; a NULL z or out (or counter /
+ * state pointer) with n > 0 returns -1 before anything is launched. */
 int dip_noise_axpy(const float* z, float* out, int64_t n, float sigma, uint64_t seed, uint64_t offset,
                    void* stream);
 

@@ -468,3 +468,63 @@ def pool2_bwd(dy, x, mode):
     dv = dx[:Hh * Ww * Cs]
     assert torch.all(dv.view(Hh, Ww, Cs)[:, :, Cc:] == 0), "pad channels must be written as zeros"
     return from_nhwc(dv, Cc, Hh, Ww)
+
+
+# ----------------------------------------------------------------------------- reg-noise
+_GUARD64 = -0x0123456789abcdef          # guard word around the counter / state words of noise_axpy
+
+
+def as_i64(v):
+    """A uint64 value as the int64 with the same bits (torch has no uint64 arithmetic)."""
+    v = int(v) & 0xffffffffffffffff
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def as_u64(v):
+    return int(v) & 0xffffffffffffffff
+
+
+def noise_state(dev, offset, seed=None):
+    """[guard, offset, guard] (dip_noise_axpy_dev) or [guard, offset, seed, guard] (dip_noise_axpy_dev2) as an int64 tensor."""
+    words = [as_i64(offset)] + ([] if seed is None else [as_i64(seed)])
+    return torch.tensor([_GUARD64] + words + [_GUARD64], dtype=torch.int64, device=dev)
+
+
+def noise_axpy(z, sigma, seed, offset, variant, z_shift=0, out_shift=0, state=None):
+    """out = z + sigma * N(0,1) over the flat float tensor z through dip_noise_axpy ("host": seed and offset by value),
+    dip_noise_axpy_dev ("dev": offset in device memory) or dip_noise_axpy_dev2 ("dev2": {offset, seed} in device memory).
+    z_shift / out_shift = 1 place the operand one float past a 16-byte boundary (the kernel's scalar path).  state: a
+    noise_state() tensor to continue the stream of an earlier device-variant call (offset, and for "dev2" seed, are ignored
+    then).  Returns (out [n], words): words is None ("host"), the counter ("dev") or (counter, seed word) ("dev2") after the
+    call, as Python ints in [0, 2^64)."""
+    lib = N.lib()
+    dev = z.device
+    n = z.numel()
+    assert z_shift in (0, 1) and out_shift in (0, 1)
+    zb = torch.zeros(n + 1, dtype=torch.float32, device=dev)
+    zb[z_shift:z_shift + n] = z.reshape(-1)
+    zkeep = zb.clone()
+    ob = guarded(out_shift + n, dev)                             # the sentinels follow out[n - 1] directly
+    zp, op = zb.data_ptr() + 4 * z_shift, ob.data_ptr() + 4 * out_shift
+    assert zb.data_ptr() % 16 == 0 and ob.data_ptr() % 16 == 0
+    st = stream(dev)
+    if variant == "host":
+        N.check(lib.dip_noise_axpy(zp, op, n, float(sigma), as_u64(seed), as_u64(offset), st), "noise_axpy")
+    elif variant == "dev":
+        state = noise_state(dev, offset) if state is None else state
+        N.check(lib.dip_noise_axpy_dev(zp, op, n, float(sigma), as_u64(seed), state.data_ptr() + 8, st), "noise_axpy_dev")
+    elif variant == "dev2":
+        state = noise_state(dev, offset, seed) if state is None else state
+        N.check(lib.dip_noise_axpy_dev2(zp, op, n, float(sigma), state.data_ptr() + 8, st), "noise_axpy_dev2")
+    else:
+        raise ValueError(variant)
+    torch.cuda.synchronize()
+    assert tail_untouched(ob), f"noise_axpy({variant}): wrote past the end of out"
+    assert bool(torch.isnan(ob[:out_shift]).all()), f"noise_axpy({variant}): wrote in front of out"
+    assert torch.equal(zb, zkeep), f"noise_axpy({variant}): z was written"
+    out = ob[out_shift:out_shift + n].clone()
+    if variant == "host":
+        return out, None
+    words = state.tolist()
+    assert words[0] == _GUARD64 and words[-1] == _GUARD64, f"noise_axpy({variant}): wrote around the counter"
+    return out, (as_u64(words[1]) if variant == "dev" else (as_u64(words[1]), as_u64(words[2])))
