@@ -17,6 +17,15 @@
 //   warm-up (fill < W), k = fill + 1:   d = x_new - mu;  mu' = mu + d / k;  M2 += d * (x_new - mu')            (Welford)
 //   window full:                        d = x_new - x_old;  mu' = mu + d / W;  M2 += d * ((x_new - mu') + (x_old - mu))
 // all in fp64; var = M2 / (W n) is rounded to fp32 only for the record, the comparison uses the fp64 value.
+//
+// The ring is 4 W n bytes (315 MB for W = 100 at 3 x 512 x 512), too much for every row of a group.  The same paper's
+// exponential-moving-variance form (ES-EMV) needs no ring: per element only the fp64 mean, and one scalar v --
+//   first output:   mu = x, v = 0
+//   afterwards:     d = x - mu;  mu' = mu + alpha d;  v' = (1 - alpha) (v + alpha sum(d^2) / n)
+// -- one load of out, one load and one store of the mean (20 n bytes against 28 n), the same partial sums, the same decision
+// and record from iteration `warmup` on (v ramps up from zero for about 1 / alpha iterations: without a warm-up the second
+// iteration is a false minimum).  dip_early_stop_emv_dev; state double[0] holds v, `fill` is 0 before the first output and 1
+// afterwards, `head` is unused.
 #include "dip_common.h"
 #include "dip_group.h"
 
@@ -78,7 +87,46 @@ __global__ __launch_bounds__(256) void early_stop_stream_kernel(const float* __r
     if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 
-// record: [var, var_min, best_iter, wait, stopped]
+// One wave sums the per-block partials in a fixed order: lane l sums blocks [l c, (l + 1) c) in block order into sh[l] ...
+__device__ __forceinline__ void es_lane_sums(const double* __restrict__ partial, int nblk, double* sh) {
+    const int c = (nblk + 63) / 64;
+    const int b0 = (int)threadIdx.x * c, b1 = b0 + c < nblk ? b0 + c : nblk;
+    double s = 0.0;
+    for (int b = b0; b < b1; ++b) s += partial[b];
+    sh[threadIdx.x] = s;
+}
+// ... and lane 0 adds the 64 lane sums in lane order
+__device__ __forceinline__ double es_total(const double* sh) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += sh[l];
+    return s;
+}
+// the decision on the fp64 variance of iteration `it` (lane 0)
+__device__ __forceinline__ void es_decide(double var, int it, int patience, int* __restrict__ state, double* __restrict__ fs) {
+    fs[2] = var;
+    if (var < fs[1]) {                            // strict; a NaN variance compares false and `wait` advances
+        fs[1] = var;
+        state[ES_BEST] = it;
+        state[ES_WAIT] = 0;
+        state[ES_IMPROVED] = 1;
+    } else {
+        const int w = state[ES_WAIT] + 1;
+        state[ES_WAIT] = w;
+        if (w >= patience) state[ES_STOPPED] = 1;
+    }
+}
+// record: [var, var_min, best_iter, wait, stopped]      (once stopped: the stopping iteration's row again)
+__device__ __forceinline__ void es_record(float* __restrict__ records, int it, const int* __restrict__ state,
+                                          const double* __restrict__ fs, int* __restrict__ counter) {
+    float* __restrict__ r = records + 5 * (int64_t)it;
+    r[0] = (float)fs[2];
+    r[1] = (float)fs[1];
+    r[2] = (float)state[ES_BEST];
+    r[3] = (float)state[ES_WAIT];
+    r[4] = (float)state[ES_STOPPED];
+    counter[0] = it + 1;
+}
+
 template <bool GRP = false>
 __global__ __launch_bounds__(64) void early_stop_finalize_kernel(const double* __restrict__ partial_, int nblk, int64_t n,
                                                                  int window, int patience, float* __restrict__ records_,
@@ -93,48 +141,88 @@ __global__ __launch_bounds__(64) void early_stop_finalize_kernel(const double* _
     const bool inside = it >= 0 && it < capacity;
     const int head = state[ES_HEAD], fill = state[ES_FILL];
     const bool live = inside && state[ES_STOPPED] == 0 && head >= 0 && head < window && fill >= 0 && fill <= window;
-    if (live) {                                   // uniform.  A fixed order: lane l sums blocks [l c, (l + 1) c) in block order ...
-        const int c = (nblk + 63) / 64;
-        const int b0 = (int)threadIdx.x * c, b1 = b0 + c < nblk ? b0 + c : nblk;
-        double s = 0.0;
-        for (int b = b0; b < b1; ++b) s += partial[b];
-        sh[threadIdx.x] = s;
-    }
+    if (live) es_lane_sums(partial, nblk, sh);    // uniform
     __syncthreads();                              // (every lane has read `state` and `counter` before lane 0 writes them)
     if (threadIdx.x != 0) return;
     double* __restrict__ fs = reinterpret_cast<double*>(state);
     state[ES_IMPROVED] = 0;
     if (!inside) return;                          // guard: the host refuses first (EarlyStopMonitor / NativeIteration)
     if (live) {
-        double s = 0.0;
-        for (int l = 0; l < 64; ++l) s += sh[l];  // ... and lane 0 adds the 64 lane sums in lane order
-        const double m2 = fs[0] + s;
+        const double m2 = fs[0] + es_total(sh);
         fs[0] = m2;
         const int f2 = fill < window ? fill + 1 : window;
         state[ES_FILL] = f2;
         state[ES_HEAD] = head + 1 == window ? 0 : head + 1;
-        if (f2 == window) {
-            const double var = m2 / ((double)window * (double)n);
-            fs[2] = var;
-            if (var < fs[1]) {                    // strict; a NaN variance compares false and `wait` advances
-                fs[1] = var;
-                state[ES_BEST] = it;
-                state[ES_WAIT] = 0;
-                state[ES_IMPROVED] = 1;
-            } else {
-                const int w = state[ES_WAIT] + 1;
-                state[ES_WAIT] = w;
-                if (w >= patience) state[ES_STOPPED] = 1;
-            }
+        if (f2 == window) es_decide(m2 / ((double)window * (double)n), it, patience, state, fs);
+    }
+    es_record(records, it, state, fs, counter);
+}
+
+// ---------------------------------------------------------------- ES-EMV: the ring-free criterion
+// One load of out, one load and one store of the fp64 mean per element; the block's partial of sum d^2.
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void early_stop_emv_stream_kernel(const float* __restrict__ out_, double* __restrict__ mean_,
+                                                                    int64_t n, double alpha, const int* __restrict__ counter_,
+                                                                    int capacity, const int* __restrict__ state_,
+                                                                    double* __restrict__ partial_, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float*, out);
+    DIP_GRP_PTR(double*, mean);
+    DIP_GRP_PTR(const int*, counter);
+    DIP_GRP_PTR(const int*, state);
+    DIP_GRP_PTR(double*, partial);
+    __shared__ double sh[256];
+    const int it = counter[0];                    // uniform; the finalize launch behind this one advances it
+    if (it < 0 || it >= capacity) return;
+    if (state[ES_STOPPED] != 0) return;           // frozen: mean and v stay what they were at the stopping iteration
+    const bool first = state[ES_FILL] == 0;       // uniform
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double xn = (double)out[i];
+        if (first) {
+            mean[i] = xn;
+        } else {
+            const double mu = mean[i];
+            const double d = xn - mu;
+            s = fma(d, d, s);
+            mean[i] = mu + alpha * d;
         }
     }
-    float* __restrict__ r = records + 5 * (int64_t)it;      // (once stopped: the stopping iteration's row again)
-    r[0] = (float)fs[2];
-    r[1] = (float)fs[1];
-    r[2] = (float)state[ES_BEST];
-    r[3] = (float)state[ES_WAIT];
-    r[4] = (float)state[ES_STOPPED];
-    counter[0] = it + 1;
+    sh[threadIdx.x] = s;
+    for (int k = 128; k >= 1; k >>= 1) {          // fixed pairing order: deterministic
+        __syncthreads();
+        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+template <bool GRP = false>
+__global__ __launch_bounds__(64) void early_stop_emv_finalize_kernel(const double* __restrict__ partial_, int nblk, int64_t n,
+                                                                     double alpha, int warmup, int patience,
+                                                                     float* __restrict__ records_, int* __restrict__ state_,
+                                                                     int* __restrict__ counter_, int capacity,
+                                                                     const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const double* __restrict__, partial);
+    DIP_GRP_PTR(float* __restrict__, records);
+    DIP_GRP_PTR(int* __restrict__, state);
+    DIP_GRP_PTR(int* __restrict__, counter);
+    __shared__ double sh[64];
+    const int it = counter[0];
+    const bool inside = it >= 0 && it < capacity;
+    const bool live = inside && state[ES_STOPPED] == 0;
+    const bool first = state[ES_FILL] == 0;
+    if (live) es_lane_sums(partial, nblk, sh);    // uniform
+    __syncthreads();                              // (every lane has read `state` and `counter` before lane 0 writes them)
+    if (threadIdx.x != 0) return;
+    double* __restrict__ fs = reinterpret_cast<double*>(state);
+    state[ES_IMPROVED] = 0;
+    if (!inside) return;                          // guard: the host refuses first
+    if (live) {
+        const double v = first ? 0.0 : (1.0 - alpha) * (fs[0] + alpha * es_total(sh) / (double)n);
+        fs[0] = v;
+        state[ES_FILL] = 1;
+        if (it >= warmup) es_decide(v, it, patience, state, fs);
+    }
+    es_record(records, it, state, fs, counter);
 }
 
 // dst <- src when the finalize kernel in front of it recorded a new minimum.  Whole quads where both buffers are 16-byte
@@ -184,6 +272,28 @@ extern "C" int dip_early_stop_dev(const DipEarlyStopDesc* d, void* stream) {
     DIP_CHECK_LAUNCH();
     dip_launch_pair<DIP_FAM_LOSS>(early_stop_finalize_kernel<false>, early_stop_finalize_kernel<true>, dim3(1), dim3(64), 0, st,
                                   (const double*)d->partial, nblk, d->n, d->window, d->patience, d->records,
+                                  reinterpret_cast<int*>(d->state), d->counter, d->capacity);
+    DIP_CHECK_LAUNCH();
+    return early_stop_keep_launch(d->out, d->best_out, d->n, reinterpret_cast<const int*>(d->state), st);
+}
+
+extern "C" int dip_early_stop_emv_dev(const DipEarlyStopEmvDesc* d, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d == nullptr) DIP_FAIL("early_stop_emv_dev: NULL descriptor");
+    if (d->out == nullptr || d->mean == nullptr || d->partial == nullptr || d->records == nullptr || d->state == nullptr ||
+        d->counter == nullptr || d->best_out == nullptr)
+        DIP_FAIL("early_stop_emv_dev: a required pointer is NULL");
+    if (d->n <= 0 || d->patience <= 0 || d->capacity <= 0 || d->warmup <= 0)
+        DIP_FAIL("early_stop_emv_dev: n, patience, capacity and warmup must be > 0");
+    if (!(d->alpha > 0.0 && d->alpha < 1.0)) DIP_FAIL("early_stop_emv_dev: alpha must be in (0, 1)");
+    if (d->n > ((int64_t)1 << 33)) DIP_FAIL("early_stop_emv_dev: n must be <= 2^33");
+    const int nblk = dip_fit_monitor_nblk(d->n);
+    dip_launch_pair<DIP_FAM_LOSS>(early_stop_emv_stream_kernel<false>, early_stop_emv_stream_kernel<true>, dim3(nblk), dim3(256), 0,
+                                  st, d->out, d->mean, d->n, d->alpha, (const int*)d->counter, d->capacity,
+                                  (const int*)d->state, d->partial);
+    DIP_CHECK_LAUNCH();
+    dip_launch_pair<DIP_FAM_LOSS>(early_stop_emv_finalize_kernel<false>, early_stop_emv_finalize_kernel<true>, dim3(1), dim3(64), 0,
+                                  st, (const double*)d->partial, nblk, d->n, d->alpha, d->warmup, d->patience, d->records,
                                   reinterpret_cast<int*>(d->state), d->counter, d->capacity);
     DIP_CHECK_LAUNCH();
     return early_stop_keep_launch(d->out, d->best_out, d->n, reinterpret_cast<const int*>(d->state), st);

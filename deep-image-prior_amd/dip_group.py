@@ -79,6 +79,22 @@ combined with downsamplers= or exp_weight= / ema_init= (this closure has no movi
     g = GroupedFits(nets, net_inputs, imgs, masks=masks, monitor=mon)
     g.capture(); g.run(num_iter - 3); mon.history()        # [B, iters, 6]: loss, mse_masked, mse, psrn_masked, psrn, fell_back
 
+When to stop, per fit and without a ground truth: `early_stop=utils.fit_monitor.GroupedEarlyStopMonitor(mode='wmv'|'emv', ...)`,
+a keyword of its own next to monitor=, independent of it, for all three group kinds (the record needs the net output only).
+Its buffers -- the ring ('wmv' only: window * n floats per instance; 'emv', the exponential moving variance, has none), the fp64
+mean, the partials, the records, the 64-byte state, the counter, best_out and, with keep_params, best_params -- are per-instance
+data of the slab behind everything else, the monitor= buffers included.  ONE dip_early_stop_dev ('emv': dip_early_stop_emv_dev)
+and ONE dip_early_stop_keep call inside the group bracket, behind the monitor's launches and in front of Adam, serve all B
+inside the ONE hipGraph of capture(); every instance takes its own decision and is bit-identical to the solo
+NativeIteration(early_stop=EarlyStopMonitor(net=...)) fit (tests/test_group_early_stop_gpu.py).  A stopped instance's early-stop
+state freezes; its fit goes on, because a row cannot leave the launch list.
+
+    mon = GroupedEarlyStopMonitor(mode='emv', alpha=0.1, patience=1000, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, early_stop=mon)
+    g.capture(); issued = 3 + g.run_until(num_iter - 3, check_every=50)     # one copy of B words and one sync per 50 iterations
+    mon.best_iter, mon.stopped                  # B ints each; mon.history() [B, iters, 5], mon.best_out [B, C, H, W]
+    mon.restore_best()                          # nets[b] carries the parameters of its minimum again (b=: one instance)
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -128,7 +144,8 @@ class GroupedFits:
     ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
-                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5):
+                 ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5,
+                 early_stop=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
@@ -143,11 +160,15 @@ class GroupedFits:
         (restoration.ipynb:192-211; no moving average either).
         tv_weights (with downsamplers= only): None, one float for all instances or B floats -- total_loss = mse(out_LR, img_LR)
         + tv_weights[b] * tv_loss(out_HR, tv_beta), the tail of SRHead(tv_weight=); all zero = None; a mix of zero and positive
-        weights is refused (an instance with weight 0 on the TV path would differ from its solo fit where s == 0)."""
+        weights is refused (an instance with weight 0 on the TV path would differ from its solo fit where s == 0).
+        early_stop: None, or a utils.fit_monitor.GroupedEarlyStopMonitor: the ground-truth-free stopping criterion per instance
+        ('wmv' or the ring-free 'emv'), inside the launch list behind monitor='s launches and in front of Adam; independent of
+        monitor= and of the group kind (the record needs the net output only).  run_until() polls it."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
         self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks)
+        self.early_stop = self._check_early_stop(early_stop)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
@@ -257,6 +278,15 @@ class GroupedFits:
                     views.update(state=self._strided(ex["mon_state"], 4),
                                  snapshot=self._strided(ex["mon_snapshot"], eng.n_arena))
                 mon._adopt(self, **views)
+            es = self.early_stop
+            if es is not None:
+                nout = ex["out"].numel()
+                es._adopt(self, records=self._strided(ex["es_records"], es.capacity, len(es.COLUMNS)),
+                          state=self._strided(ex["es_state"], 16), counter=self._strided(ex["es_counter"]),
+                          best_out=self._strided(ex["es_best_out"], *hr),
+                          best_params=self._strided(ex["es_best_params"], eng.n_arena),
+                          ring=self._strided(ex["es_ring"], es.window, nout), mean=self._strided(ex["es_mean"], nout),
+                          partial=self._strided(ex["es_partial"], ex["es_partial"].numel()))
             self._nbt_all = self._strided(eng.nbt, eng.nbt.numel())
             if not self._dry:
                 torch.cuda.synchronize(device)
@@ -304,6 +334,20 @@ class GroupedFits:
         elif not restore:                               # (the restoration monitor brings no images: target and mask are the group's)
             monitor._check_targets(targets)
         return monitor
+
+    @staticmethod
+    def _check_early_stop(early_stop):
+        """What can be said about `early_stop` before anything is planned or allocated."""
+        if early_stop is None:
+            return None
+        from utils.fit_monitor import GroupedEarlyStopMonitor
+        if not isinstance(early_stop, GroupedEarlyStopMonitor):
+            raise TypeError(f"dip-amd: GroupedFits(early_stop=) takes a utils.fit_monitor.GroupedEarlyStopMonitor or None, got "
+                            f"{type(early_stop).__name__} (a solo EarlyStopMonitor owns its buffers: they are no rows of the slab)")
+        if early_stop._adopted:
+            raise RuntimeError("dip-amd: this GroupedEarlyStopMonitor already belongs to a GroupedFits (a monitor is adopted "
+                               "once)")
+        return early_stop
 
     @staticmethod
     def _check_tv(tv_weights, tv_beta, B, downsamplers):
@@ -391,6 +435,9 @@ class GroupedFits:
         if self.monitor is not None:
             visit("fit_monitor", "desc", self._mdesc)
             pointer_args(self._mon)
+        if self.early_stop is not None:
+            visit("early_stop", "desc", self._edesc)
+            pointer_args(self._es)
         for k, t in self._row0_extra.items():
             if t is not None:
                 visit("extra", k, t.data_ptr())
@@ -475,6 +522,8 @@ class GroupedFits:
         self._head_fwd, self._head_bwd = fwd(eng, self._head), bwd(eng, self._head, at("gl"))
         if self.monitor is not None:
             self._build_row0_monitor(slab)
+        if self.early_stop is not None:
+            self._build_row0_early_stop(slab)
 
     def _build_row0_monitor(self, slab):
         """The monitor's buffers, behind everything else instance 0 owns: what utils.fit_monitor.FitMonitor (super-resolution:
@@ -517,6 +566,32 @@ class GroupedFits:
         self._mdesc = FM.fit_monitor_descriptor(m, ex["out"], ex["target"], ex["mon_gt"], ex["mon_avg"], ex["mon_partial"],
                                                 ex["mon_records"], ex["mon_counter"], ex["mon_state"], ex["loss"])
         self._mon = FM.fit_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena, snapshot_ptr())
+
+    def _build_row0_early_stop(self, slab):
+        """The early-stopping buffers, behind everything else instance 0 owns (monitor='s buffers included): what
+        utils.fit_monitor.EarlyStopMonitor allocates for a solo fit, as per-instance data of the slab -- 'emv' has no ring --
+        ONE descriptor over them (out = the head's output) and the launches of an iteration.  The state is initialised in both
+        passes, so the row copy carries it to every instance."""
+        from utils import fit_monitor as FM
+        eng, lib, ex, es = self.eng, self.lib, self._row0_extra, self.early_stop
+        nout = ex["out"].numel()
+        emv = es.mode == "emv"
+        ex["es_ring"] = None if emv else slab.alloc(es.window * nout)
+        ex["es_mean"] = slab.alloc(nout, torch.float64)
+        ex["es_partial"] = slab.alloc(lib.dip_fit_monitor_nblk(nout), torch.float64)
+        ex["es_records"] = slab.alloc(es.capacity * 5, zero=True)
+        ex["es_state"] = FM.early_stop_state_fill(slab.alloc(16, torch.int32))
+        ex["es_counter"] = slab.alloc(1, torch.int32, zero=True)
+        ex["es_best_out"] = slab.alloc(nout, zero=True)
+        ex["es_best_params"] = slab.alloc(eng.n_arena, zero=True) if es.keep_params else None
+        bufs = (ex["es_mean"], ex["es_partial"], ex["es_records"], ex["es_state"], ex["es_counter"], ex["es_best_out"])
+        if emv:
+            self._edesc = FM.early_stop_emv_descriptor(es, ex["out"], *bufs)
+        else:
+            self._edesc = FM.early_stop_descriptor(es, ex["out"], ex["es_ring"], *bufs, ex["loss"])
+        best = ex["es_best_params"]
+        self._es = FM.early_stop_launches(lib, self._edesc, eng.params.data_ptr(), eng.n_arena,
+                                          None if best is None else best.data_ptr())
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()
@@ -596,6 +671,11 @@ class GroupedFits:
             if self.monitor is not None:
                 for fn, args, name in self._mon:
                     N.check(fn(*args, st), name)
+            # es.update(out): behind the monitor (a fall-back has been applied), in front of Adam -- best_params are the
+            # parameters that produced best_out; every instance takes its own decision
+            if self.early_stop is not None:
+                for fn, args, name in self._es:
+                    N.check(fn(*args, st), name)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
             N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")
             N.check(lib.dip_adam_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(), ex["v"].data_ptr(),
@@ -613,14 +693,16 @@ class GroupedFits:
                 self.out_avg.mul_(self.exp_weight).add_(self.out, alpha=1 - self.exp_weight)
 
     def _check_room(self, n):
-        """The monitor refuses n more iterations that do not fit its records, before anything is issued."""
-        if self.monitor is not None:
-            self.monitor._check_room(n)
+        """The monitors refuse n more iterations that do not fit their records, before anything is issued."""
+        for m in (self.monitor, self.early_stop):
+            if m is not None:
+                m._check_room(n)
 
     def _issued(self, n):
         self.iterations += n
-        if self.monitor is not None:
-            self.monitor.i += n
+        for m in (self.monitor, self.early_stop):
+            if m is not None:
+                m.i += n
 
     def step(self, n=1):
         """n eager iterations (launches on the current stream + the engine's auxiliary streams)."""
@@ -656,6 +738,27 @@ class GroupedFits:
         for _ in range(int(n)):
             self.graph.replay()
         self._issued(int(n))
+
+    def run_until(self, max_iter, check_every=50):
+        """Runs until every instance's early stopping says stop, or max_iter: issues run(check_every) batches, eager or
+        replayed, and reads the B `stopped` words after each batch (one copy and one synchronisation per batch).  Returns the
+        iterations issued.  A stopped instance keeps training until the last one stops -- a row cannot leave the launch list --
+        but its best_out / best_params are frozen (early_stop.restore_best() puts the minima back)."""
+        es = self.early_stop
+        if es is None:
+            raise RuntimeError("dip-amd: GroupedFits.run_until needs early_stop=GroupedEarlyStopMonitor(...)")
+        max_iter, check_every = max(int(max_iter), 0), int(check_every)
+        if check_every < 1:
+            raise ValueError(f"dip-amd: run_until: check_every must be >= 1, got {check_every}")
+        self._check_room(max_iter)                # (before anything is issued, as run(max_iter) would)
+        issued = 0
+        while issued < max_iter:
+            n = min(check_every, max_iter - issued)
+            self.run(n)
+            issued += n
+            if all(es.stopped):
+                break
+        return issued
 
     def step_counts(self):
         """Adam's step count of every instance, as the device holds it."""

@@ -148,6 +148,15 @@ class DipEarlyStopDesc(C.Structure):
                 ("loss", C.c_void_p)]
 
 
+class DipEarlyStopEmvDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("mean", C.c_void_p), ("partial", C.c_void_p), ("records", C.c_void_p),
+                ("state", C.c_void_p), ("counter", C.c_void_p), ("best_out", C.c_void_p), ("n", C.c_int64),
+                ("alpha", C.c_double), ("warmup", C.c_int32), ("patience", C.c_int32), ("capacity", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(DipEarlyStopDesc) == 96 and C.sizeof(DipEarlyStopEmvDesc) == 88          # include/dip_hip.h states both
+
 _SIGS = {
     "dip_abi_version": (C.c_int, []),
     "dip_build_id": (C.c_char_p, []),
@@ -300,6 +309,7 @@ _SIGS = {
     "dip_restore_monitor_dev": (C.c_int, [C.POINTER(DipRestoreMonitorDesc), C.c_void_p]),
     "dip_early_stop_dev": (C.c_int, [C.POINTER(DipEarlyStopDesc), C.c_void_p]),
     "dip_early_stop_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "dip_early_stop_emv_dev": (C.c_int, [C.POINTER(DipEarlyStopEmvDesc), C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),
     "dip_lanczos_down_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

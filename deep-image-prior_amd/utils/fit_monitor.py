@@ -94,6 +94,18 @@ finalize, a conditional copy; columns var, var_min, best_iter, wait, stopped), a
     it = NativeIteration(net, head, opt, net_input, reg_noise=reg, early_stop=es)   # next to monitor=, independent of it
     issued, losses = it.run_until(num_iter, check_every=50)                         # one 4-byte read per 50 iterations
     es.best_iter, es.best_out; es.restore_best()                                    # the net carries the minimum's parameters
+
+The ring is 4 * window * n bytes.  mode='emv' is the ring-free form of the same paper, the exponential moving variance
+(dip_early_stop_emv_dev): only the fp64 mean is carried per element, 20 n bytes of traffic instead of 28 n, decisions from
+iteration `warmup` on.  That is what a group can afford in every row: B fits through one launch list take a
+GroupedEarlyStopMonitor (settings only, adopted once; either mode), and every instance takes its own decision:
+
+    es = EarlyStopMonitor(img_noisy_torch, patience=1000, net=net, capacity=num_iter, mode='emv', alpha=0.1)    # no ring
+
+    mon = GroupedEarlyStopMonitor(mode='emv', alpha=0.1, patience=1000, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, early_stop=mon)   # next to monitor=, independent of it
+    g.capture(); issued = g.run_until(num_iter - 3, check_every=50)                     # until ALL instances have stopped
+    mon.best_iter, mon.stopped, mon.best_out[b]; mon.restore_best()                     # per instance; the minima's parameters
 The reference's per-iteration cost this replaces: three `.detach().cpu().numpy()` of the output, a
 `.item()`, and -- whenever `i % show_every` is non-zero -- a copy of all 2.2 M parameters to the CPU.
 """
@@ -470,7 +482,12 @@ class RestorationFitMonitor(_DeviceRecords):
 def early_stop_state(dev):
     """The 64-byte state of dip_early_stop_dev before the first iteration, as int32[16]: var_min = var = +inf (double[1],
     double[2]), best_iter = -1 (int32[9]), everything else zero."""
-    st = torch.zeros(16, dtype=torch.int32, device=dev)
+    return early_stop_state_fill(torch.zeros(16, dtype=torch.int32, device=dev))
+
+
+def early_stop_state_fill(st):
+    """Writes that state into `st` (int32[16], 8-byte aligned; a row of a group's slab) and returns it."""
+    st.zero_()
     st.view(torch.float64)[1:3] = float("inf")
     st[9] = -1
     return st
@@ -483,11 +500,43 @@ def early_stop_descriptor(m, out, ring, mean, partial, records, state, counter, 
 
 
 def early_stop_launches(lib, desc, params_ptr, n_arena, best_params_ptr):
-    """dip_early_stop_dev and, with a best_params arena, dip_early_stop_keep as (fn, args, name) triples."""
-    es = [(lib.dip_early_stop_dev, (C.byref(desc),), "early_stop_dev")]
+    """The entry point of `desc` -- dip_early_stop_dev, or dip_early_stop_emv_dev for a DipEarlyStopEmvDesc -- and, with a
+    best_params arena, dip_early_stop_keep as (fn, args, name) triples."""
+    emv = isinstance(desc, N.DipEarlyStopEmvDesc)
+    es = [(lib.dip_early_stop_emv_dev if emv else lib.dip_early_stop_dev, (C.byref(desc),),
+           "early_stop_emv_dev" if emv else "early_stop_dev")]
     if best_params_ptr is not None:
         es.append((lib.dip_early_stop_keep, (params_ptr, best_params_ptr, n_arena, desc.state), "early_stop_keep"))
     return es
+
+
+def early_stop_emv_descriptor(m, out, mean, partial, records, state, counter, best_out):
+    """DipEarlyStopEmvDesc of monitor m (alpha, warmup, patience, capacity) over these buffers: no ring, no loss."""
+    return N.DipEarlyStopEmvDesc(_ptr(out), _ptr(mean), _ptr(partial), _ptr(records), _ptr(state), _ptr(counter), _ptr(best_out),
+                                 out.numel(), m.alpha, m.warmup, m.patience, m.capacity, 0)
+
+
+def _early_stop_settings(who, mode, window, alpha, warmup, patience, capacity):
+    """(mode, window, alpha, warmup, patience, capacity) of an early-stopping monitor, or the ValueError that says what is
+    wrong: needs no GPU.  `window` belongs to 'wmv' and is not looked at in 'emv'; warmup=None is ceil(2 / alpha) -- v starts
+    at zero and ramps up for about 1 / alpha iterations, and a decision taken on the ramp is a false minimum."""
+    if mode not in ("wmv", "emv"):
+        raise ValueError(f"dip-amd: {who}: mode is 'wmv' (windowed moving variance) or 'emv' (exponential moving variance), "
+                         f"got {mode!r}")
+    if mode == "wmv" and int(window) < 2:
+        raise ValueError(f"dip-amd: {who}: window must be >= 2, got {window}")
+    if int(patience) < 1:
+        raise ValueError(f"dip-amd: {who}: patience must be >= 1, got {patience}")
+    if int(capacity) < 1 or int(capacity) > 2 ** 24:
+        raise ValueError(f"dip-amd: {who}: capacity must be in [1, 2**24] (best_iter is a float32 column), got "
+                         f"{capacity}")
+    if not 0.0 < float(alpha) < 1.0:                                # (a NaN compares false)
+        raise ValueError(f"dip-amd: {who}: alpha must be in (0, 1), got {alpha}")
+    if warmup is None:
+        warmup = int(np.ceil(2.0 / float(alpha)))
+    if int(warmup) < 1 or int(warmup) > 2 ** 24:
+        raise ValueError(f"dip-amd: {who}: warmup must be in [1, 2**24], got {warmup}")
+    return mode, int(window), float(alpha), int(warmup), int(patience), int(capacity)
 
 
 class EarlyStopMonitor(_DeviceRecords):
@@ -505,30 +554,30 @@ class EarlyStopMonitor(_DeviceRecords):
     `counter`, the ring head and the fill count from `state`), and the two may alternate.
 
     Memory: the ring holds `window` outputs, 4 * window * n bytes -- 315 MB for window = 100 at 3 x 512 x 512 -- plus 8 n bytes
-    of fp64 mean and 4 n of best_out (`memory_bytes`)."""
+    of fp64 mean and 4 n of best_out (`memory_bytes`).
+
+    mode='emv' is the ring-free form of the same paper, the exponential moving variance (dip_early_stop_emv_dev): mu <- mu +
+    alpha (x - mu), v <- (1 - alpha) (v + alpha |x - mu|^2 / n), decisions on v from iteration `warmup` on (None: ceil(2 /
+    alpha); v ramps up from zero for about 1 / alpha iterations and a decision on the ramp is a false minimum).  The same
+    record, the same state, best_out / best_params / restore_best() / run_until; `ring` is None and `window` is ignored: 8 n
+    bytes of mean plus 4 n of best_out, 9.4 MB at 3 x 512 x 512."""
     COLUMNS = ("var", "var_min", "best_iter", "wait", "stopped")
     head_kind = None                                                # any head: the record needs the net output only
 
-    def __init__(self, img_like, window=100, patience=1000, net=None, capacity=16384):
+    def __init__(self, img_like, window=100, patience=1000, net=None, capacity=16384, *, mode="wmv", alpha=0.1, warmup=None):
         # (what needs no GPU is refused first: the settings, the net)
         if not isinstance(img_like, torch.Tensor):
             raise TypeError("dip-amd: EarlyStopMonitor: img_like is a tensor shaped like the net output ([1,C,H,W])")
-        if int(window) < 2:
-            raise ValueError(f"dip-amd: EarlyStopMonitor: window must be >= 2, got {window}")
-        if int(patience) < 1:
-            raise ValueError(f"dip-amd: EarlyStopMonitor: patience must be >= 1, got {patience}")
-        if int(capacity) < 1 or int(capacity) > 2 ** 24:
-            raise ValueError(f"dip-amd: EarlyStopMonitor: capacity must be in [1, 2**24] (best_iter is a float32 column), got "
-                             f"{capacity}")
+        self.mode, self.window, self.alpha, self.warmup, self.patience, capacity = _early_stop_settings(
+            "EarlyStopMonitor", mode, window, alpha, warmup, patience, capacity)
         self._init_backtracking(net, net is not None)               # `engine`: the net's, or None without net=
         if not img_like.is_cuda:
             raise RuntimeError("dip-amd: EarlyStopMonitor works on MI355X tensors only (no CPU fallback)")
         self._init_records(img_like.device, capacity)
-        self.window, self.patience = int(window), int(patience)
         self.shape, self.n = tuple(img_like.shape), img_like.numel()
         if self.n < 1:
             raise ValueError("dip-amd: EarlyStopMonitor: img_like is empty")
-        self.ring = torch.empty((self.window, self.n), dtype=torch.float32, device=self.dev)
+        self.ring = torch.empty((self.window, self.n), dtype=torch.float32, device=self.dev) if self.mode == "wmv" else None
         self.mean = torch.empty(self.n, dtype=torch.float64, device=self.dev)
         self.partial = torch.empty(self.lib.dip_fit_monitor_nblk(self.n), dtype=torch.float64, device=self.dev)
         self.state = early_stop_state(self.dev)
@@ -537,7 +586,7 @@ class EarlyStopMonitor(_DeviceRecords):
 
     @property
     def memory_bytes(self):
-        """Device memory this monitor holds (the ring dominates: 4 * window * n)."""
+        """Device memory this monitor holds ('wmv': the ring dominates, 4 * window * n; 'emv' has none)."""
         ts = (self.ring, self.mean, self.partial, self.state, self.best_out, self.records, self.counter, self.best_params)
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
@@ -594,33 +643,38 @@ class EarlyStopMonitor(_DeviceRecords):
         with torch.cuda.device(self.dev):        # raw HIP launches go to the current device's streams
             stream = torch.cuda.current_stream(self.dev).cuda_stream
             self._sync_counter()
-            desc = self._dev_descriptor(o)
-            N.check(self.lib.dip_early_stop_dev(C.byref(desc), stream), "early_stop_dev")
-            best = self._ensure_best_params()
-            if best is not None:
-                params = self.engine.params
-                N.check(self.lib.dip_early_stop_keep(params.data_ptr(), best.data_ptr(), params.numel(),
-                                                     self.state.data_ptr(), stream), "early_stop_keep")
+            for fn, args, name in self._launches(self._dev_descriptor(o)):
+                N.check(fn(*args, stream), name)
         self._keep = o
         self._advance(1)
 
     # ------------------------------------------------------------------ the form inside dip_optim.NativeIteration(early_stop=)
     def _dev_descriptor(self, out):
-        """DipEarlyStopDesc over this monitor's buffers for the output buffer `out`."""
+        """DipEarlyStopDesc ('emv': DipEarlyStopEmvDesc) over this monitor's buffers for the output buffer `out`."""
+        if self.mode == "emv":
+            return early_stop_emv_descriptor(self, out, self.mean, self.partial, self.records, self.state, self.counter,
+                                             self.best_out)
         return early_stop_descriptor(self, out, self.ring, self.mean, self.partial, self.records, self.state, self.counter,
                                      self.best_out)
+
+    def _launches(self, desc):
+        """The mode's entry point over `desc` and, with net=, dip_early_stop_keep over the parameter arena."""
+        if self.engine is None:
+            return early_stop_launches(self.lib, desc, None, 0, None)
+        params = self.engine.params
+        return early_stop_launches(self.lib, desc, params.data_ptr(), params.numel(), _ptr(self._ensure_best_params()))
 
     def _plan(self, eng, out, head):
         """(descriptor, launches) of an iteration that writes the net output to `out` (dip_optim.NativeIteration)."""
         self._check_out(out.shape, "NativeIteration")
         desc = self._dev_descriptor(out)
-        return desc, early_stop_launches(self.lib, desc, eng.params.data_ptr(), eng.params.numel(),
-                                         _ptr(self._ensure_best_params()))
+        return desc, self._launches(desc)
 
     def _plan_key(self):
         """What a compiled command array (dip_optim.NativeIteration) was built from: buffers by identity, settings by value."""
         return (id(self), id(self.records), id(self.state), id(self.ring), id(self.mean), id(self.partial), id(self.best_out),
-                id(self.best_params), id(self.counter), self.window, self.patience, id(self.engine), self.capacity, self.n)
+                id(self.best_params), id(self.counter), self.window, self.patience, id(self.engine), self.capacity, self.n,
+                self.mode, self.alpha, self.warmup)
 
     def _plan_keep(self):
         """The objects behind _plan_key and every buffer the descriptor points to: alive as long as the plan."""
@@ -746,3 +800,69 @@ class GroupedSRFitMonitor(_GroupedRecords):
     def _check_hr(self, B, hr_shape):
         """imgs_HR against the planned net output: one [1,C,H,W] image per instance."""
         self._check_images(self.imgs_HR, [hr_shape] * B, "imgs_HR", "the net output")
+
+
+class GroupedEarlyStopMonitor(_GroupedRecords):
+    """EarlyStopMonitor for the B fits of a dip_group.GroupedFits(..., early_stop=this): settings only.  A keyword of its own
+    next to monitor=, independent of it, for all three group kinds (plain, masks=, downsamplers=): the record needs the net
+    output only.  The group that adopts it places, behind everything else a row owns -- the monitor= buffers included -- the
+    ring ('wmv' only), the fp64 mean, the partials, the records, the 64-byte state, the counter, best_out and, with
+    keep_params, best_params, and exposes them here as [B, ...] views: records [B, capacity, 5], state [B, 16] int32, counter
+    [B], best_out [B, C, H, W], best_params [B, n_arena] (None with keep_params=False), ring [B, window, n] (None in 'emv')
+    and mean [B, n].  ONE dip_early_stop_dev ('emv': dip_early_stop_emv_dev) and ONE dip_early_stop_keep call inside the group
+    bracket, behind the monitor= launches and in front of Adam, serve all B inside the ONE hipGraph of capture().
+
+    Every instance takes its own decision.  A stopped instance's early-stop state is frozen; its fit goes on, because a row
+    cannot leave the launch list: g.run_until() returns once ALL instances have stopped, restore_best() puts every minimum back.
+    mode='emv' is what a group can afford in every row: 12 n bytes per instance instead of 4 * window * n."""
+    COLUMNS = EarlyStopMonitor.COLUMNS
+
+    def __init__(self, mode="wmv", window=100, alpha=0.1, warmup=None, patience=1000, keep_params=True, capacity=16384):
+        self.mode, self.window, self.alpha, self.warmup, self.patience, capacity = _early_stop_settings(
+            "GroupedEarlyStopMonitor", mode, window, alpha, warmup, patience, capacity)
+        self.keep_params = bool(keep_params)
+        self._init_group(capacity)
+        self.state = self.best_out = self.best_params = self.ring = self.mean = self.partial = None
+
+    def _views(self):
+        if self.state is None:
+            raise RuntimeError("dip-amd: this GroupedEarlyStopMonitor has not been given to a GroupedFits yet")
+        return (self.ring, self.mean, self.partial, self.records, self.state, self.counter, self.best_out, self.best_params)
+
+    @property
+    def memory_bytes(self):
+        """Device memory the B instances hold for early stopping (as EarlyStopMonitor.memory_bytes, times B)."""
+        return sum(t.numel() * t.element_size() for t in self._views() if t is not None)
+
+    @property
+    def best_iter(self):
+        """The iteration of every instance's minimum, -1 before its first decision: B ints (one copy; synchronises)."""
+        return self._views()[4][:, 9].tolist()
+
+    @property
+    def stopped(self):
+        """Per instance, 1 once `patience` iterations passed without a new minimum: B ints (one copy; synchronises)."""
+        return self._views()[4][:, 10].tolist()
+
+    def restore_best(self, b=None):
+        """Copies best_params back over the parameter row of instance b (None: of every instance): nets[b] then produces
+        best_out[b] again."""
+        self._views()
+        g = self.group
+        if g is None:
+            raise RuntimeError("dip-amd: GroupedEarlyStopMonitor.restore_best: the GroupedFits that adopted this monitor is gone")
+        if self.best_params is None:
+            raise RuntimeError("dip-amd: GroupedEarlyStopMonitor.restore_best needs keep_params=True (the monitor keeps best_out "
+                               "only)")
+        rows = range(g.B) if b is None else [int(b)]
+        if any(not 0 <= r < g.B for r in rows):
+            raise IndexError(f"dip-amd: GroupedEarlyStopMonitor.restore_best: instance {b} of {g.B}")
+        best = self.best_iter
+        none = [r for r in rows if best[r] < 0]
+        if none:
+            raise RuntimeError(f"dip-amd: GroupedEarlyStopMonitor.restore_best: no minimum has been recorded yet for instance(s) "
+                               f"{none}")
+        params = g._strided(g.eng.params, g.eng.n_arena)
+        with torch.no_grad():
+            for r in rows:
+                params[r].copy_(self.best_params[r])

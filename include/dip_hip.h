@@ -870,7 +870,7 @@ int dip_restore_monitor_dev(const DipRestoreMonitorDesc* d, void* stream);
  * monitors' (dip_optim.NativeIteration rewrites it per iteration).  Every other pointer is required; n, window, patience,
  * capacity > 0 and window >= 2, otherwise -1 before anything is launched.  sizeof(DipEarlyStopDesc) == 96 (LP64).
  * The kernels have grouped instantiations (family DIP_FAM_LOSS: every non-NULL pointer in instance 0's slab, instance b works
- * on the same fields advanced by b * stride); GroupedFits does not use them yet.
+ * on the same fields advanced by b * stride); dip_group.GroupedFits(early_stop=) issues them inside its group bracket.
  * dip_early_stop_keep: dst <- src (n floats, any n, any 4-byte alignment; whole quads only where both are 16-byte aligned)
  * when state's `improved` is set, else nothing: issued behind dip_early_stop_dev over the flat parameter arena, it keeps the
  * parameters that produced best_out. */
@@ -889,6 +889,42 @@ typedef struct DipEarlyStopDesc {
 } DipEarlyStopDesc;
 int dip_early_stop_dev(const DipEarlyStopDesc* d, void* stream);
 int dip_early_stop_keep(const float* src, float* dst, int64_t n, const void* state, void* stream);
+
+/* The ring-free form of the same criterion: the exponential moving variance of the output (ES-EMV, the same paper).  Per fit
+ * only the fp64 mean [n] and one scalar v are carried -- no [window][n] ring -- so a group can afford it in every row.
+ * Outputs x_0, x_1, ..., alpha in (0, 1), warmup >= 1, patience P >= 1, all arithmetic fp64:
+ *   t = 0:                        mu <- x_0, v <- 0
+ *   t >= 1, while not stopped:    d = x_t - mu;  mu <- mu + alpha d;  v <- (1 - alpha) (v + alpha sum(d^2) / n)
+ *   t >= warmup, while not stopped: var_t = v and the decision of dip_early_stop_dev --
+ *             var_t < var_min (strict): var_min <- var_t, best_iter <- t, wait <- 0, best_out <- x_t, improved <- 1
+ *             otherwise:                wait <- wait + 1;  wait >= P: stopped <- 1
+ *   record <- {var, var_min, best_iter, wait, stopped}; rows before `warmup` are {inf, inf, -1, 0, 0}, rows after the stopping
+ *             iteration repeat its row.  Once stopped, mu, v, var_min, best_iter and best_out are frozen.
+ * v starts at zero and ramps up for about 1 / alpha iterations: with warmup = 1 the second iteration is a false minimum
+ * (utils.fit_monitor defaults to ceil(2 / alpha)).  A NaN output makes v NaN: no minimum is taken and wait advances.
+ * ONE streaming pass (256 threads, grid-stride, dip_fit_monitor_nblk(n) blocks): one load of out, one load and one store of
+ * the mean -- 20 n bytes of traffic against the 28 n of the windowed form -- one fp64 fma into the thread's partial of sum d^2,
+ * the 256-wide LDS tree in the fixed pairing order, one fp64 partial per block; then the one-wave finalize in the fixed lane
+ * order of dip_early_stop_dev and the same conditional copy into best_out.  Deterministic, no float atomics, nothing synchronises.
+ * state: the 64-byte layout of dip_early_stop_dev with double[0] = v; the int words keep their meaning (fill: 0 before the
+ * first output, 1 afterwards); `head` is unused.  t is counter[0]; t outside [0, capacity): nothing but improved <- 0 is written.
+ * Every pointer is required; n, patience, capacity, warmup > 0, alpha in (0, 1), n <= 2^33, otherwise -1 before anything is
+ * launched.  The loss is no part of the record, so the descriptor has no `loss` field (DipEarlyStopDesc carries one that is not
+ * read).  sizeof(DipEarlyStopEmvDesc) == 88 (LP64).  Grouped instantiations: family DIP_FAM_LOSS.
+ * dip_early_stop_keep keeps the parameter arena of the minimum, as behind dip_early_stop_dev. */
+typedef struct DipEarlyStopEmvDesc {
+    const float* out;       /* [n] the network output of this iteration */
+    double* mean;           /* [n] fp64 exponential moving mean */
+    double* partial;        /* dip_fit_monitor_nblk(n) doubles of scratch */
+    float* records;         /* [capacity][5] */
+    void* state;            /* 64 bytes, see above */
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    float* best_out;        /* [n] the output at the minimum */
+    int64_t n;
+    double alpha;
+    int warmup, patience, capacity, reserved;
+} DipEarlyStopEmvDesc;
+int dip_early_stop_emv_dev(const DipEarlyStopEmvDesc* d, void* stream);
 
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
