@@ -28,6 +28,7 @@
 // afterwards, `head` is unused.
 #include "dip_common.h"
 #include "dip_group.h"
+#include "monitor_common.h"
 
 namespace {
 
@@ -50,9 +51,8 @@ __global__ __launch_bounds__(256) void early_stop_stream_kernel(const float* __r
     DIP_GRP_PTR(const int*, counter);
     DIP_GRP_PTR(const int*, state);
     DIP_GRP_PTR(double*, partial);
-    __shared__ double sh[256];
     const int it = counter[0];                    // uniform; the finalize launch behind this one advances it
-    if (it < 0 || it >= capacity) return;         // the overflow guard of restore_monitor_*
+    if (!mon_in_range(it, capacity)) return;
     if (state[ES_STOPPED] != 0) return;           // frozen: ring, mean and M2 stay what they were at the stopping iteration
     const int head = state[ES_HEAD], fill = state[ES_FILL];
     if (head < 0 || head >= window || fill < 0 || fill > window) return;          // (a state the host did not initialise)
@@ -79,12 +79,7 @@ __global__ __launch_bounds__(256) void early_stop_stream_kernel(const float* __r
         slot[i] = x;
         mean[i] = mu2;
     }
-    sh[threadIdx.x] = s;
-    for (int k = 128; k >= 1; k >>= 1) {          // fixed pairing order: deterministic
-        __syncthreads();
-        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+    mon_block_sum(s, partial + blockIdx.x);
 }
 
 // One wave sums the per-block partials in a fixed order: lane l sums blocks [l c, (l + 1) c) in block order into sh[l] ...
@@ -138,7 +133,7 @@ __global__ __launch_bounds__(64) void early_stop_finalize_kernel(const double* _
     DIP_GRP_PTR(int* __restrict__, counter);
     __shared__ double sh[64];
     const int it = counter[0];
-    const bool inside = it >= 0 && it < capacity;
+    const bool inside = mon_in_range(it, capacity);
     const int head = state[ES_HEAD], fill = state[ES_FILL];
     const bool live = inside && state[ES_STOPPED] == 0 && head >= 0 && head < window && fill >= 0 && fill <= window;
     if (live) es_lane_sums(partial, nblk, sh);    // uniform
@@ -170,9 +165,8 @@ __global__ __launch_bounds__(256) void early_stop_emv_stream_kernel(const float*
     DIP_GRP_PTR(const int*, counter);
     DIP_GRP_PTR(const int*, state);
     DIP_GRP_PTR(double*, partial);
-    __shared__ double sh[256];
     const int it = counter[0];                    // uniform; the finalize launch behind this one advances it
-    if (it < 0 || it >= capacity) return;
+    if (!mon_in_range(it, capacity)) return;
     if (state[ES_STOPPED] != 0) return;           // frozen: mean and v stay what they were at the stopping iteration
     const bool first = state[ES_FILL] == 0;       // uniform
     double s = 0.0;
@@ -187,12 +181,7 @@ __global__ __launch_bounds__(256) void early_stop_emv_stream_kernel(const float*
             mean[i] = mu + alpha * d;
         }
     }
-    sh[threadIdx.x] = s;
-    for (int k = 128; k >= 1; k >>= 1) {          // fixed pairing order: deterministic
-        __syncthreads();
-        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+    mon_block_sum(s, partial + blockIdx.x);
 }
 
 template <bool GRP = false>
@@ -207,7 +196,7 @@ __global__ __launch_bounds__(64) void early_stop_emv_finalize_kernel(const doubl
     DIP_GRP_PTR(int* __restrict__, counter);
     __shared__ double sh[64];
     const int it = counter[0];
-    const bool inside = it >= 0 && it < capacity;
+    const bool inside = mon_in_range(it, capacity);
     const bool live = inside && state[ES_STOPPED] == 0;
     const bool first = state[ES_FILL] == 0;
     if (live) es_lane_sums(partial, nblk, sh);    // uniform

@@ -12,6 +12,7 @@
 // it wants to print.
 #include "dip_common.h"
 #include "dip_group.h"
+#include "monitor_common.h"
 
 namespace {
 
@@ -36,7 +37,7 @@ __device__ __forceinline__ void fit_monitor_partials_body(const float* __restric
     __shared__ float sh[3][256];
     if constexpr (DEV) {
         const int it = counter[0];                // uniform; the finalize launch behind this one advances it
-        if (it < 0 || it >= capacity) return;
+        if (it < 0 || it >= capacity) return;     // (not mon_in_range: in front of `first` it compiles to other code)
         first = it == 0;
     }
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
@@ -53,7 +54,7 @@ __device__ __forceinline__ void fit_monitor_partials_body(const float* __restric
         }
     }
     sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1; sh[2][threadIdx.x] = s2;
-    for (int s = 128; s >= 1; s >>= 1) {          // fixed pairing order: deterministic
+    for (int s = 128; s >= 1; s >>= 1) {          // (not mon_block_sum: a three-sum form of it compiles to other code)
         __syncthreads();
         if ((int)threadIdx.x < s) {
 #pragma unroll
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* _
     int it = 0;
     if constexpr (DEV) {
         it = counter[0];
-        if (it < 0 || it >= capacity) {           // guard: the host refuses first (FitMonitor / NativeIteration)
+        if (!mon_in_range(it, capacity)) {        // guard: the host refuses first
             state[1] = 0.f;
             state[3] = 0.f;
             return;
@@ -116,24 +117,12 @@ __global__ __launch_bounds__(64) void fit_monitor_finalize_kernel(const float* _
     float mse[3], psnr[3];
     for (int k = 0; k < 3; ++k) {
         mse[k] = (float)(s[k] / (double)n);
-        psnr[k] = (float)(-10.0 * log10(s[k] / (double)n));      // data_range = 1
+        psnr[k] = mon_psnr(s[k], n);
     }
     record[0] = loss != nullptr ? loss[0] : 0.f;
     record[1] = mse[0]; record[2] = have_gt ? mse[1] : 0.f; record[3] = have_gt ? mse[2] : 0.f;
     record[4] = psnr[0]; record[5] = have_gt ? psnr[1] : 0.f; record[6] = have_gt ? psnr[2] : 0.f;
-    float restore = 0.f, snap = 0.f;
-    if (check) {
-        if (state[2] != 0.f && psnr[0] - state[0] < -thresh_db) {
-            restore = 1.f;                                        // "Falling back to previous checkpoint."
-        } else {
-            snap = 1.f;
-            state[0] = psnr[0];
-            state[2] = 1.f;
-        }
-    }
-    state[1] = restore;
-    state[3] = snap;
-    record[7] = restore;
+    record[7] = mon_backtrack_decision(state, check, psnr[0], thresh_db);
     if constexpr (DEV) counter[0] = it + 1;
 }
 

@@ -18,6 +18,7 @@
 // written into its row and the index moves on (the notebook returns before its `i += 1` and tests again at its next call).
 #include "dip_common.h"
 #include "dip_group.h"
+#include "monitor_common.h"
 
 namespace {
 
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void restore_monitor_partials_kernel(const flo
     __shared__ float sh[2][256];
     if constexpr (DEV) {
         const int it = counter[0];                // uniform; the finalize launch behind this one advances it
-        if (it < 0 || it >= capacity) return;
+        if (!mon_in_range(it, capacity)) return;
     }
     const bool plane = mask_c == 1;               // uniform
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void restore_monitor_partials_kernel(const flo
         if (p >= hw) p -= hw;
     }
     sh[0][threadIdx.x] = s0; sh[1][threadIdx.x] = s1;
-    for (int s = 128; s >= 1; s >>= 1) {          // fixed pairing order: deterministic
+    for (int s = 128; s >= 1; s >>= 1) {          // (not mon_block_sum: a two-sum form of it compiles to other code)
         __syncthreads();
         if ((int)threadIdx.x < s) {
             sh[0][threadIdx.x] += sh[0][threadIdx.x + s];
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(64) void restore_monitor_finalize_kernel(const floa
     int it = 0;
     if constexpr (DEV) {
         it = counter[0];
-        if (it < 0 || it >= capacity) {           // guard: the host refuses first (RestorationFitMonitor / NativeIteration)
+        if (!mon_in_range(it, capacity)) {        // guard: the host refuses first
             state[1] = 0.f;
             state[3] = 0.f;
             return;
@@ -111,24 +112,12 @@ __global__ __launch_bounds__(64) void restore_monitor_finalize_kernel(const floa
     float mse[2], psnr[2];
     for (int k = 0; k < 2; ++k) {
         mse[k] = (float)(s[k] / (double)n);                      // compare_psnr over the whole array (:192-193)
-        psnr[k] = (float)(-10.0 * log10(s[k] / (double)n));      // data_range = 1
+        psnr[k] = mon_psnr(s[k], n);
     }
     record[0] = loss != nullptr ? loss[0] : 0.f;
     record[1] = mse[0]; record[2] = mse[1];
     record[3] = psnr[0]; record[4] = psnr[1];
-    float restore = 0.f, snap = 0.f;
-    if (check) {
-        if (state[2] != 0.f && psnr[0] - state[0] < -thresh_db) {
-            restore = 1.f;                                        // "Falling back to previous checkpoint." (:202-208)
-        } else {
-            snap = 1.f;                                           // (:209-211)
-            state[0] = psnr[0];
-            state[2] = 1.f;
-        }
-    }
-    state[1] = restore;
-    state[3] = snap;
-    record[5] = restore;
+    record[5] = mon_backtrack_decision(state, check, psnr[0], thresh_db);       // restoration.ipynb:202-211
     if constexpr (DEV) counter[0] = it + 1;
 }
 

@@ -9,6 +9,7 @@
 // the records when it wants the curve.  No EMA and no back-tracking: this closure has neither (monitor_kernels.hip has both).
 #include "dip_common.h"
 #include "dip_group.h"
+#include "monitor_common.h"
 
 namespace {
 
@@ -34,10 +35,9 @@ __global__ __launch_bounds__(256) void sr_monitor_partials_kernel(const float* _
     DIP_GRP_PTR(const float*, img_lr);
     DIP_GRP_PTR(const int*, counter);
     DIP_GRP_PTR(float*, partial);
-    __shared__ float sh[256];
     if constexpr (DEV) {
         const int it = counter[0];                // uniform; the finalize launch behind this one advances it
-        if (it < 0 || it >= capacity) return;
+        if (!mon_in_range(it, capacity)) return;
     }
     const bool hr = (int)blockIdx.x < nblk_hr;    // workgroup-uniform
     const float* __restrict__ a = hr ? out_hr : out_lr;
@@ -50,12 +50,7 @@ __global__ __launch_bounds__(256) void sr_monitor_partials_kernel(const float* _
         const float d = a[i] - b[i];
         s = fmaf(d, d, s);
     }
-    sh[threadIdx.x] = s;
-    for (int w = 128; w >= 1; w >>= 1) {          // fixed pairing order: deterministic
-        __syncthreads();
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+    mon_block_sum(s, partial + blockIdx.x);
 }
 
 // record: [loss, mse_LR, mse_HR, psnr_LR, psnr_HR]
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(64) void sr_monitor_finalize_kernel(const float* __
     int it = 0;
     if constexpr (DEV) {
         it = counter[0];
-        if (it < 0 || it >= capacity) return;     // guard: the host refuses first (SRFitMonitor / NativeIteration / GroupedFits)
+        if (!mon_in_range(it, capacity)) return;  // guard: the host refuses first (SRFitMonitor / NativeIteration / GroupedFits)
         record += 5 * (int64_t)it;
     }
     double h = 0.0, l = 0.0;
@@ -93,8 +88,8 @@ __global__ __launch_bounds__(64) void sr_monitor_finalize_kernel(const float* __
     record[0] = loss != nullptr ? loss[0] : 0.f;
     record[1] = (float)(l / (double)n_lr);
     record[2] = have_hr ? (float)(h / (double)n_hr) : 0.f;
-    record[3] = (float)(-10.0 * log10(l / (double)n_lr));        // data_range = 1
-    record[4] = have_hr ? (float)(-10.0 * log10(h / (double)n_hr)) : 0.f;
+    record[3] = mon_psnr(l, n_lr);
+    record[4] = have_hr ? mon_psnr(h, n_hr) : 0.f;
     if constexpr (DEV) counter[0] = it + 1;
 }
 

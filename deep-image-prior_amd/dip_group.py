@@ -168,7 +168,7 @@ class GroupedFits:
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
         self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks)
-        self.early_stop = self._check_early_stop(early_stop)
+        self.early_stop = self._check_monitor_slot(early_stop, "early_stop")
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
@@ -268,25 +268,12 @@ class GroupedFits:
             self.out = self._strided(ex["out"], *hr)
             self.out_LR = self._strided(ex.get("y"), *t0.shape[1:])
             self.out_avg = torch.zeros((B,) + hr, dtype=torch.float32, device=device) if self.exp_weight is not None else None
-            if mon is not None:
-                views = dict(records=self._strided(ex["mon_records"], mon.capacity, len(mon.COLUMNS)),
-                             counter=self._strided(ex["mon_counter"]))
-                if "mon_avg" in ex:                          # GroupedFitMonitor: the monitor carries the moving average
-                    self.out_avg = self._strided(ex["mon_avg"], *hr)
-                    views.update(out_avg=self.out_avg)
-                if "mon_state" in ex:                        # the back-tracking monitors (denoising, restoration)
-                    views.update(state=self._strided(ex["mon_state"], 4),
-                                 snapshot=self._strided(ex["mon_snapshot"], eng.n_arena))
-                mon._adopt(self, **views)
-            es = self.early_stop
-            if es is not None:
-                nout = ex["out"].numel()
-                es._adopt(self, records=self._strided(ex["es_records"], es.capacity, len(es.COLUMNS)),
-                          state=self._strided(ex["es_state"], 16), counter=self._strided(ex["es_counter"]),
-                          best_out=self._strided(ex["es_best_out"], *hr),
-                          best_params=self._strided(ex["es_best_params"], eng.n_arena),
-                          ring=self._strided(ex["es_ring"], es.window, nout), mean=self._strided(ex["es_mean"], nout),
-                          partial=self._strided(ex["es_partial"], ex["es_partial"].numel()))
+            for m, prefix, _, _ in self._monitors():          # the [B, ...] views a grouped monitor exposes, from its table
+                z = self._monitor_sizes(m)
+                shape = lambda b: b.shape(z) if b.shape else (b.count(z),)
+                m._adopt(self, **{b.name: self._strided(ex[prefix + (b.key or b.name)], *shape(b)) for b in m.BUFFERS if b.view})
+            if getattr(mon, "out_avg", None) is not None:     # GroupedFitMonitor: the monitor carries the moving average
+                self.out_avg = mon.out_avg
             self._nbt_all = self._strided(eng.nbt, eng.nbt.numel())
             if not self._dry:
                 torch.cuda.synchronize(device)
@@ -295,16 +282,39 @@ class GroupedFits:
     def _devctx(self):
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
 
+    _SLOTS = (("monitor", "mon_", "_mdesc", "_mon"), ("early_stop", "es_", "_edesc", "_es"))
+
+    def _monitors(self):
+        """The monitors of this group in launch order -- monitor=, then early_stop=, both in front of Adam -- as (monitor, the
+        prefix of its slab rows' names, the attribute of its descriptor, the attribute of its launches)."""
+        return [(getattr(self, slot), *rest) for slot, *rest in self._SLOTS if getattr(self, slot) is not None]
+
     @staticmethod
-    def _check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks=None):
-        """What can be said about `monitor` before anything is planned or allocated."""
+    def _check_monitor_slot(m, slot):
+        """What holds for monitor= and early_stop= alike: the types the slot takes, and that a monitor is adopted once."""
+        import utils.fit_monitor as FM
+        if m is None:
+            return None
+        if slot == "early_stop":
+            if not isinstance(m, FM.GroupedEarlyStopMonitor):
+                raise TypeError(f"dip-amd: GroupedFits(early_stop=) takes a utils.fit_monitor.GroupedEarlyStopMonitor or None, got "
+                                f"{type(m).__name__} (a solo EarlyStopMonitor owns its buffers: they are no rows of the slab)")
+        elif not isinstance(m, (FM.GroupedFitMonitor, FM.GroupedSRFitMonitor, FM.GroupedRestorationFitMonitor)):
+            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor, a "
+                            f"GroupedRestorationFitMonitor or None, got {type(m).__name__} (a solo FitMonitor cannot "
+                            "checkpoint a slab row)")
+        if m._adopted:
+            raise RuntimeError(f"dip-amd: this {type(m).__name__} already belongs to a GroupedFits (a monitor is adopted once)")
+        return m
+
+    @classmethod
+    def _check_monitor(cls, monitor, downsamplers, exp_weight, ema_init, targets, masks=None):
+        """What can be said about `monitor` before anything is planned or allocated: the slot's checks, then the group kind
+        its record belongs to."""
+        from utils.fit_monitor import GroupedRestorationFitMonitor, GroupedSRFitMonitor
         if monitor is None:
             return None
-        from utils.fit_monitor import GroupedFitMonitor, GroupedRestorationFitMonitor, GroupedSRFitMonitor
-        if not isinstance(monitor, (GroupedFitMonitor, GroupedSRFitMonitor, GroupedRestorationFitMonitor)):
-            raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor, a "
-                            f"GroupedRestorationFitMonitor or None, got {type(monitor).__name__} (a solo FitMonitor cannot "
-                            "checkpoint a slab row)")
+        cls._check_monitor_slot(monitor, "monitor")
         sr, restore = isinstance(monitor, GroupedSRFitMonitor), isinstance(monitor, GroupedRestorationFitMonitor)
         if restore and downsamplers is not None:
             raise NotImplementedError("dip-amd: GroupedFits(monitor=GroupedRestorationFitMonitor) with downsamplers= is not "
@@ -326,28 +336,11 @@ class GroupedFits:
                              ("the super-resolution closure has no moving average of the output)" if sr else
                               "the restoration closure has no moving average of the output)" if restore else
                               "the monitor carries exp_weight and starts out_avg from the first output)"))
-        if monitor._adopted:
-            raise RuntimeError(f"dip-amd: this {type(monitor).__name__} already belongs to a GroupedFits (a monitor is adopted "
-                               "once)")
         if sr:
-            monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _build_row0_monitor)
+            monitor._check_count(len(targets))          # (the shapes: when the net output is planned, _carve_monitor)
         elif not restore:                               # (the restoration monitor brings no images: target and mask are the group's)
             monitor._check_targets(targets)
         return monitor
-
-    @staticmethod
-    def _check_early_stop(early_stop):
-        """What can be said about `early_stop` before anything is planned or allocated."""
-        if early_stop is None:
-            return None
-        from utils.fit_monitor import GroupedEarlyStopMonitor
-        if not isinstance(early_stop, GroupedEarlyStopMonitor):
-            raise TypeError(f"dip-amd: GroupedFits(early_stop=) takes a utils.fit_monitor.GroupedEarlyStopMonitor or None, got "
-                            f"{type(early_stop).__name__} (a solo EarlyStopMonitor owns its buffers: they are no rows of the slab)")
-        if early_stop._adopted:
-            raise RuntimeError("dip-amd: this GroupedEarlyStopMonitor already belongs to a GroupedFits (a monitor is adopted "
-                               "once)")
-        return early_stop
 
     @staticmethod
     def _check_tv(tv_weights, tv_beta, B, downsamplers):
@@ -432,12 +425,9 @@ class GroupedFits:
 
         visit("sr_loss" if self.downsamplers is not None else "loss_head", "desc", self._head)
         pointer_args(self._head_fwd + self._head_bwd)
-        if self.monitor is not None:
-            visit("fit_monitor", "desc", self._mdesc)
-            pointer_args(self._mon)
-        if self.early_stop is not None:
-            visit("early_stop", "desc", self._edesc)
-            pointer_args(self._es)
+        for _, prefix, desc, ops in self._monitors():
+            visit("fit_monitor" if prefix == "mon_" else "early_stop", "desc", getattr(self, desc))
+            pointer_args(getattr(self, ops))
         for k, t in self._row0_extra.items():
             if t is not None:
                 visit("extra", k, t.data_ptr())
@@ -458,7 +448,7 @@ class GroupedFits:
     def _build_row0(self, slab, Cimg, H, W, t0, m0):
         """Everything instance 0 owns, in a fixed order, from `slab`: the engine's buffers, the closure's input, the loss head's
         buffers -- those of utils.loss_head.MSEHead, or of SRHead -- with its descriptor and launches, the closure's end and,
-        behind everything else, the monitor's buffers."""
+        behind everything else, the monitors' buffers."""
         from utils import loss_head as LH
         eng, lib, sr, tv = self.eng, self.lib, self.downsamplers is not None, self.tv_weights is not None
         eng.slab = slab
@@ -520,78 +510,41 @@ class GroupedFits:
         # dip_head_fwd writes out_HR as net(x) does)
         self._with_out_conv = sr
         self._head_fwd, self._head_bwd = fwd(eng, self._head), bwd(eng, self._head, at("gl"))
-        if self.monitor is not None:
-            self._build_row0_monitor(slab)
-        if self.early_stop is not None:
-            self._build_row0_early_stop(slab)
+        for m, prefix, desc, ops in self._monitors():
+            d, launches = self._carve_monitor(slab, m, prefix)
+            setattr(self, desc, d)
+            setattr(self, ops, launches)
 
-    def _build_row0_monitor(self, slab):
-        """The monitor's buffers, behind everything else instance 0 owns: what utils.fit_monitor.FitMonitor (super-resolution:
-        SRFitMonitor) allocates for a solo fit, as per-instance data of the slab; ONE descriptor over them (the outputs = the
-        head's, noisy / img_LR = the target, loss = the slab's loss scalar: nothing is rewritten per iteration) and the
-        launches of an iteration."""
+    def _monitor_sizes(self, m):
+        from utils.fit_monitor import monitor_sizes
+        eng, ex = self.eng, self._row0_extra
+        return monitor_sizes(m, self.lib.dip_fit_monitor_nblk, ex["out"].numel(), (eng.n_out, eng.Hout, eng.Wout), (),
+                             n_lr=None if ex.get("y") is None else ex["y"].numel(), n_arena=eng.n_arena)
+
+    def _carve_monitor(self, slab, m, prefix):
+        """The buffers of monitor m (monitor= or early_stop=) behind everything instance 0 owns so far: what the solo monitor of
+        its kind allocates for one fit -- its table, utils.fit_monitor -- as per-instance data of the slab under the names
+        prefix + key (None where m has no such buffer); ONE descriptor over them (the outputs = the head's, noisy / img / img_LR
+        = the target, mask = the group's, loss = the slab's loss scalar: nothing is rewritten per iteration) and the launches
+        of an iteration.  Both passes initialise the buffers, so the row copy carries them to every instance."""
         from utils import fit_monitor as FM
-        eng, lib, ex, m = self.eng, self.lib, self._row0_extra, self.monitor
-        nout = ex["out"].numel()
-        if self.downsamplers is not None:
+        eng, ex = self.eng, self._row0_extra
+        if self.downsamplers is not None and prefix == "mon_":
             m._check_hr(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
-            ex["mon_hr"] = slab.alloc(nout) if m.imgs_HR is not None else None
-            ex["mon_partial"] = slab.alloc(lib.dip_fit_monitor_nblk(nout) + lib.dip_fit_monitor_nblk(ex["y"].numel()))
-            ex["mon_records"] = slab.alloc(m.capacity * 5, zero=True)
-            ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
-            self._mdesc = FM.sr_monitor_descriptor(m, ex["out"], ex["y"], ex["mon_hr"], ex["target"], ex["mon_partial"],
-                                                   ex["mon_records"], ex["mon_counter"], ex["loss"])
-            self._mon = FM.sr_monitor_launches(lib, self._mdesc)
-            return
-        snapshot_ptr = lambda: None if ex["mon_snapshot"] is None else ex["mon_snapshot"].data_ptr()
-        if isinstance(m, FM.GroupedRestorationFitMonitor):
-            # (restoration.ipynb:192-211; img and mask are the group's own target and mask rows: no second copy)
-            ex["mon_partial"] = slab.alloc(2 * lib.dip_fit_monitor_nblk(nout))
-            ex["mon_records"] = slab.alloc(m.capacity * 6, zero=True)
-            ex["mon_state"] = slab.alloc(4, zero=True)
-            ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
-            ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
-            self._mdesc = FM.restore_monitor_descriptor(m, ex["out"], ex["target"], ex["mask"], self.mask_c, eng.Hout * eng.Wout,
-                                                        ex["mon_partial"], ex["mon_records"], ex["mon_counter"], ex["mon_state"],
-                                                        ex["loss"])
-            self._mon = FM.restore_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena, snapshot_ptr())
-            return
-        ex["mon_gt"] = slab.alloc(nout) if m.imgs_gt is not None else None
-        ex["mon_avg"] = slab.alloc(nout, zero=True)
-        ex["mon_partial"] = slab.alloc(4 * lib.dip_fit_monitor_nblk(nout))
-        ex["mon_records"] = slab.alloc(m.capacity * 8, zero=True)
-        ex["mon_state"] = slab.alloc(4, zero=True)
-        ex["mon_counter"] = slab.alloc(1, torch.int32, zero=True)
-        ex["mon_snapshot"] = slab.alloc(eng.n_arena) if m.backtracking else None
-        self._mdesc = FM.fit_monitor_descriptor(m, ex["out"], ex["target"], ex["mon_gt"], ex["mon_avg"], ex["mon_partial"],
-                                                ex["mon_records"], ex["mon_counter"], ex["mon_state"], ex["loss"])
-        self._mon = FM.fit_monitor_launches(lib, self._mdesc, eng.params.data_ptr(), eng.n_arena, snapshot_ptr())
-
-    def _build_row0_early_stop(self, slab):
-        """The early-stopping buffers, behind everything else instance 0 owns (monitor='s buffers included): what
-        utils.fit_monitor.EarlyStopMonitor allocates for a solo fit, as per-instance data of the slab -- 'emv' has no ring --
-        ONE descriptor over them (out = the head's output) and the launches of an iteration.  The state is initialised in both
-        passes, so the row copy carries it to every instance."""
-        from utils import fit_monitor as FM
-        eng, lib, ex, es = self.eng, self.lib, self._row0_extra, self.early_stop
-        nout = ex["out"].numel()
-        emv = es.mode == "emv"
-        ex["es_ring"] = None if emv else slab.alloc(es.window * nout)
-        ex["es_mean"] = slab.alloc(nout, torch.float64)
-        ex["es_partial"] = slab.alloc(lib.dip_fit_monitor_nblk(nout), torch.float64)
-        ex["es_records"] = slab.alloc(es.capacity * 5, zero=True)
-        ex["es_state"] = FM.early_stop_state_fill(slab.alloc(16, torch.int32))
-        ex["es_counter"] = slab.alloc(1, torch.int32, zero=True)
-        ex["es_best_out"] = slab.alloc(nout, zero=True)
-        ex["es_best_params"] = slab.alloc(eng.n_arena, zero=True) if es.keep_params else None
-        bufs = (ex["es_mean"], ex["es_partial"], ex["es_records"], ex["es_state"], ex["es_counter"], ex["es_best_out"])
-        if emv:
-            self._edesc = FM.early_stop_emv_descriptor(es, ex["out"], *bufs)
-        else:
-            self._edesc = FM.early_stop_descriptor(es, ex["out"], ex["es_ring"], *bufs, ex["loss"])
-        best = ex["es_best_params"]
-        self._es = FM.early_stop_launches(lib, self._edesc, eng.params.data_ptr(), eng.n_arena,
-                                          None if best is None else best.data_ptr())
+        z = self._monitor_sizes(m)
+        t = dict(out=ex["out"], out_LR=ex.get("y"), noisy=ex["target"], img=ex["target"], img_LR=ex["target"], mask=ex["mask"],
+                 mask_c=self.mask_c, hw=eng.Hout * eng.Wout, loss=ex["loss"])
+        for b in m.BUFFERS:
+            buf = None
+            if b.when(m):
+                buf = slab.alloc(b.count(z), b.dtype, zero=b.init == "zero")
+                if b.init == "early_stop":
+                    FM.early_stop_state_fill(buf)
+            t[b.name] = ex[prefix + (b.key or b.name)] = buf
+        desc = m._descriptor(t)
+        arena = t[m.ARENA[0]] if m.ARENA else None
+        return desc, FM.monitor_launches(self.lib, desc, eng.params.data_ptr(), eng.n_arena,
+                                         None if arena is None else arena.data_ptr())
 
     def _off(self, t0):
         o = t0.data_ptr() - self.mem.data_ptr()
@@ -668,13 +621,10 @@ class GroupedFits:
             # monitor.update(out, total_loss): EMA, PSNRs, record; a fall-back overwrites the parameters after this
             # iteration's gradients and before Adam (denoising.ipynb:238-248), per instance
             # (super-resolution: monitor.update(out_HR, out_LR, total_loss): the psnr_LR / psnr_HR record)
-            if self.monitor is not None:
-                for fn, args, name in self._mon:
-                    N.check(fn(*args, st), name)
             # es.update(out): behind the monitor (a fall-back has been applied), in front of Adam -- best_params are the
             # parameters that produced best_out; every instance takes its own decision
-            if self.early_stop is not None:
-                for fn, args, name in self._es:
+            for _, _, _, ops in self._monitors():
+                for fn, args, name in getattr(self, ops):
                     N.check(fn(*args, st), name)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
             N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")
@@ -694,15 +644,13 @@ class GroupedFits:
 
     def _check_room(self, n):
         """The monitors refuse n more iterations that do not fit their records, before anything is issued."""
-        for m in (self.monitor, self.early_stop):
-            if m is not None:
-                m._check_room(n)
+        for m, *_ in self._monitors():
+            m._check_room(n)
 
     def _issued(self, n):
         self.iterations += n
-        for m in (self.monitor, self.early_stop):
-            if m is not None:
-                m.i += n
+        for m, *_ in self._monitors():
+            m.i += n
 
     def step(self, n=1):
         """n eager iterations (launches on the current stream + the engine's auxiliary streams)."""

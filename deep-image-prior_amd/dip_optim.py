@@ -405,8 +405,7 @@ class NativeIteration:
         # (the monitor's type is refused before the first check that needs a GPU)
         self.monitor, self.device = monitor, getattr(net_input, "device", None)
         self.early_stop = early_stop
-        self._check_monitor()
-        self._check_early_stop()
+        self._check_monitors()
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
                                "fallback)")
@@ -428,7 +427,7 @@ class NativeIteration:
             if reg_noise.saved.shape != net_input.shape or reg_noise.saved.device != net_input.device:
                 raise ValueError("dip-amd: the RegNoise was built for another net_input")
         self.head, self.opt = head, optimizer
-        self._check_monitor()                     # (now with the head: an SRFitMonitor records the two outputs of an SRHead)
+        self._check_monitors()                    # (now with the head: an SRFitMonitor records the two outputs of an SRHead)
         self.net_input, self.reg = net_input.detach(), reg_noise
         self.out = None
         self.iterations = 0
@@ -446,57 +445,48 @@ class NativeIteration:
         if not self.net.training:
             raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
 
-    def _check_monitor(self):
-        """What can be said about `monitor` before the output size is known (the image shape: _build)."""
-        from utils.fit_monitor import FitMonitor, RestorationFitMonitor, SRFitMonitor
-        m = self.monitor
-        if m is None:
-            return
-        if not isinstance(m, (FitMonitor, SRFitMonitor, RestorationFitMonitor)):
-            raise TypeError("dip-amd: monitor must be a utils.fit_monitor.FitMonitor, an SRFitMonitor, a RestorationFitMonitor or "
-                            f"None, got {type(m).__name__}")
-        head = getattr(self, "head", None)
-        if head is not None and m.head_kind not in (None, head.kind):
-            raise TypeError(f"dip-amd: an SRFitMonitor records out_LR and out_HR of a utils.loss_head.SRHead, the head is a "
-                            f"{type(head).__name__} (use a FitMonitor)")
-        if m.dev != self.device:
-            raise RuntimeError(f"dip-amd: the {type(m).__name__} lives on {m.dev}, the iteration runs on {self.device}")
-        if m.engine is not None and m.engine is not self.engine:
-            raise ValueError(f"dip-amd: the {type(m).__name__} back-tracks another net (it was built for a different skip() net)")
+    def _monitors(self):
+        """The monitors of this iteration in launch order -- monitor=, then early_stop=, both in front of Adam -- as (slot,
+        monitor) pairs."""
+        return [(slot, getattr(self, slot)) for slot in ("monitor", "early_stop") if getattr(self, slot) is not None]
 
-    def _check_early_stop(self):
-        """What can be said about `early_stop` before the output size is known (the image shape: _build)."""
-        from utils.fit_monitor import EarlyStopMonitor
-        es = self.early_stop
-        if es is None:
-            return
-        if not isinstance(es, EarlyStopMonitor):
-            raise TypeError(f"dip-amd: early_stop must be a utils.fit_monitor.EarlyStopMonitor or None, got {type(es).__name__}")
-        if es.dev != self.device:
-            raise RuntimeError(f"dip-amd: the EarlyStopMonitor lives on {es.dev}, the iteration runs on {self.device}")
-        if es.engine is not None and es.engine is not self.engine:
-            raise ValueError("dip-amd: the EarlyStopMonitor keeps the parameters of another net (it was built with a different "
-                             "skip() net)")
+    def _check_monitors(self):
+        """What can be said about monitor= and early_stop= before the output size is known (the image shape: _build)."""
+        import utils.fit_monitor as FM
+        takes = {"monitor": ((FM.FitMonitor, FM.SRFitMonitor, FM.RestorationFitMonitor), "dip-amd: monitor must be a "
+                             "utils.fit_monitor.FitMonitor, an SRFitMonitor, a RestorationFitMonitor or None", "back-tracks"),
+                 "early_stop": (FM.EarlyStopMonitor, "dip-amd: early_stop must be a utils.fit_monitor.EarlyStopMonitor or None",
+                                "keeps the parameters of")}
+        head = getattr(self, "head", None)
+        for slot, m in self._monitors():
+            types, refusal, copies = takes[slot]
+            if not isinstance(m, types):
+                raise TypeError(f"{refusal}, got {type(m).__name__}")
+            if head is not None and m.head_kind not in (None, head.kind):
+                raise TypeError(f"dip-amd: an SRFitMonitor records out_LR and out_HR of a utils.loss_head.SRHead, the head is a "
+                                f"{type(head).__name__} (use a FitMonitor)")
+            if m.dev != self.device:
+                raise RuntimeError(f"dip-amd: the {type(m).__name__} lives on {m.dev}, the iteration runs on {self.device}")
+            if m.engine is not None and m.engine is not self.engine:
+                raise ValueError(f"dip-amd: the {type(m).__name__} {copies} another net (it was built for a different skip() net)")
 
     # -------------------------------------------------------------------------------------------- the command arrays
     def _signature(self, sig):
         """Everything a slot of the command arrays was computed from.  Objects by identity: the arrays hold raw pointers, and
         the plan keeps every object of its key alive, so neither an id nor an address can be recycled unnoticed."""
-        eng, head, opt, reg, m, es = self.engine, self.head, self.opt, self.reg, self.monitor, self.early_stop
+        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
         # (an engine that has never planned has no op lists yet: None never equals a built key)
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
                 opt.lr, opt.betas, opt.eps, id(opt._groups),
                 head._plan_key(),
                 None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
-            + (() if m is None else (m._plan_key(),)) \
-            + (() if es is None else (("early_stop", es._plan_key()),))          # (None: the key as it was)
+            + tuple((slot, m._plan_key()) for slot, m in self._monitors())       # (no monitors: the key as it was)
 
     def _build(self):
-        eng, head, opt, reg, m, es = self.engine, self.head, self.opt, self.reg, self.monitor, self.early_stop
+        eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
         lib = N.lib()
         dev = self.device
-        self._check_monitor()
-        self._check_early_stop()
+        self._check_monitors()
         noisy = reg is not None and reg.std > 0
         x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
         _, Cimg, H, W = x.shape
@@ -530,53 +520,42 @@ class NativeIteration:
                                                  b1, b2, float(opt.eps), st.data_ptr()), "adam_step_dev"))
         on_main = lambda ops: N.CmdList([("launch", fn, args, 0, name) for fn, args, name in ops])
         phases = [on_main(pre), fwd, on_main(mid), bwd, on_main(adam)]
-        mdesc = None
-        if m is not None:
-            # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the
-            # parameters after this iteration's gradients were computed and before Adam applies them
-            # (the monitor checks its images against the outputs -- an SRHead's LR buffer exists now -- and says what it launches)
-            mdesc, mon = m._plan(eng, out, head)
+        # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the parameters
+        # after this iteration's gradients were computed and before Adam applies them; es.update(out)'s place is behind it
+        # (the fall-back has been applied: the arena it keeps holds the parameters that produced `out`).  Each monitor checks
+        # its images against the outputs -- an SRHead's LR buffer exists now -- and says what it launches.
+        descs = {}
+        for slot, m in self._monitors():
+            descs[slot], ops = m._plan(eng, out, head)
+            phases.insert(len(phases) - 1, on_main(ops))
+        mdesc = descs.get("monitor")
+        if mdesc is not None:
             mdesc.loss = loss0.data_ptr()
-            phases.insert(4, on_main(mon))
-        edesc = None
-        if es is not None:
-            # es.update(out)'s place: behind the monitor (a fall-back has been applied), in front of Adam -- the arena it keeps
-            # holds the parameters that produced `out`
-            edesc, stop = es._plan(eng, out, head)
-            phases.insert(len(phases) - 1, on_main(stop))
         lists = N.IterList(phases)
         views = [eng.grads[o:o + p.numel()].view(p.shape) for p, o in zip(eng.param_list, eng.slots)]
         self.out = out
         # everything a slot points to stays alive with the plan, and so does every object whose id is part of the key
-        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, edesc=edesc, views=views, x=x, state=st, loss0=loss0,
+        self._plan = dict(lists=lists, desc=desc, mdesc=mdesc, edesc=descs.get("early_stop"), views=views, x=x, state=st,
+                          loss0=loss0,
                           keep=(head._plan_keep(), eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
                                 None if reg is None else (reg.saved, reg.out, reg.offset),
-                                None if m is None else m._plan_keep(), None if es is None else es._plan_keep()))
+                                [m._plan_keep() for _, m in self._monitors()]))
         self._key = self._signature(opt._sig)
 
     # -------------------------------------------------------------------------------------------- run
     def _begin(self, n=1):
         self._check_training()
         self._check_capture()
-        self._check_monitor()                     # (`it.monitor` may have been replaced)
-        self._check_early_stop()
+        self._check_monitors()                    # (`it.monitor` may have been replaced)
         self.head._check_state()                  # (an SRHead's down-sampler may have become trainable)
-        m = self.monitor
-        if m is not None and m.i + n > m.capacity:
-            raise RuntimeError(f"dip-amd: {type(m).__name__} capacity exceeded ({m.i} recorded + {n} > capacity {m.capacity}); "
-                               "construct it with capacity >= num_iter")
-        es = self.early_stop
-        if es is not None and es.i + n > es.capacity:
-            raise RuntimeError(f"dip-amd: EarlyStopMonitor capacity exceeded ({es.i} recorded + {n} > capacity {es.capacity}); "
-                               "construct it with capacity >= num_iter")
+        for _, m in self._monitors():
+            m._check_room(n)
         # (the parameters' addresses are part of the key: they also say that the engine's arena still holds the parameters)
         if self._signature(self.opt._signature()) != self._key:
             self._build()
-        if m is not None:
+        for _, m in self._monitors():
             m._sync_counter()                     # eager update() calls in between: the device index follows monitor.i
-        if es is not None:
-            es._sync_counter()
         eng = self.engine
         ptrs = [torch.cuda.current_stream(self.device).cuda_stream]
         if eng.two_streams:
@@ -598,10 +577,8 @@ class NativeIteration:
         eng.last_out, eng.last_head = self.out, self.head
         self.opt.step_count += n
         self.iterations += n
-        if self.monitor is not None:
-            self.monitor._advance(n)
-        if self.early_stop is not None:
-            self.early_stop._advance(n)
+        for _, m in self._monitors():
+            m._advance(n)
 
     @torch.no_grad()
     def step(self):
@@ -645,9 +622,7 @@ class NativeIteration:
         max_iter, check_every = max(int(max_iter), 0), int(check_every)
         if check_every < 1:
             raise ValueError(f"dip-amd: run_until: check_every must be >= 1, got {check_every}")
-        if es.i + max_iter > es.capacity:          # (before anything is issued, as run(max_iter) would)
-            raise RuntimeError(f"dip-amd: EarlyStopMonitor capacity exceeded ({es.i} recorded + {max_iter} > capacity "
-                               f"{es.capacity}); construct it with capacity >= num_iter")
+        es._check_room(max_iter)                   # (before anything is issued, as run(max_iter) would)
         parts, issued = [], 0
         while issued < max_iter:
             n = min(check_every, max_iter - issued)
