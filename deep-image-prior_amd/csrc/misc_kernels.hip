@@ -189,6 +189,27 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2])
     k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
 }
 
+// The four normals of Philox quad `ctr` under key `seed`: the reg-noise stream (noise_axpy_kernel) and the SGLD stream
+// (adam_sgld_kernel) are this one function of (key, quad).
+__device__ __forceinline__ void philox_normals4(uint64_t ctr, uint64_t seed, float (&nrm)[4]) {
+    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+#pragma unroll
+    for (int r = 0; r < 10; ++r) philox_round(c, k);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // (0,1]: 2^-25 for word >> 8 == 0; from 2^23 up the + 0.5f ties to even, and 2^24 - 1 gives exactly 1.0 (radius 0).
+        // DESIGN.md "The reg-noise stream" is the specification; tests/noise_ref.py restates it in numpy.
+        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float rad = sqrtf(-2.0f * __logf(u1));
+        float s, co;
+        __sincosf(6.28318530717958647692f * u2, &s, &co);
+        nrm[2 * h] = rad * co;
+        nrm[2 * h + 1] = rad * s;
+    }
+}
+
 // SEED_DEV: the seed, too, lives in device memory (offset_dev[1]): grouped fits with one stream per instance
 template <bool GRP = false, bool SEED_DEV = false>
 __global__ __launch_bounds__(256) void noise_axpy_kernel(const float* __restrict__ z_, float* __restrict__ out_,
@@ -202,23 +223,8 @@ __global__ __launch_bounds__(256) void noise_axpy_kernel(const float* __restrict
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one Philox block = 4 normals
     const int64_t i0 = q * 4;
     if (i0 >= n) return;
-    uint32_t c[4] = {(uint32_t)(q + offset), (uint32_t)((uint64_t)(q + offset) >> 32), 0u, 0u};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < 10; ++r) philox_round(c, k);
     float nrm[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        // (0,1]: 2^-25 for word >> 8 == 0; from 2^23 up the + 0.5f ties to even, and 2^24 - 1 gives exactly 1.0 (radius 0).
-        // DESIGN.md "The reg-noise stream" is the specification; tests/noise_ref.py restates it in numpy.
-        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float rad = sqrtf(-2.0f * __logf(u1));
-        float s, co;
-        __sincosf(6.28318530717958647692f * u2, &s, &co);
-        nrm[2 * h] = rad * co;
-        nrm[2 * h + 1] = rad * s;
-    }
+    philox_normals4((uint64_t)(q + offset), seed, nrm);
     if (i0 + 3 < n && ((reinterpret_cast<uintptr_t>(z + i0) | reinterpret_cast<uintptr_t>(out + i0)) & 15) == 0) {
         const f32x4 zv = *reinterpret_cast<const f32x4*>(z + i0);
         f32x4 o;
@@ -227,6 +233,113 @@ __global__ __launch_bounds__(256) void noise_axpy_kernel(const float* __restrict
         *reinterpret_cast<f32x4*>(out + i0) = o;
     } else {
         for (int e = 0; e < 4 && i0 + e < n; ++e) out[i0 + e] = fmaf(sigma, nrm[e], z[i0 + e]);
+    }
+}
+
+// ---------------------------------------------------------------- Adam + weight decay + SGLD parameter noise, one pass
+// Per element (include/dip_hip.h: dip_adam_sgld_step_dev is the specification):
+//   g' = wd != 0 ? fmaf(wd, p, g) : g         (ATen's grad.add(param, alpha=wd): one rounding)
+//   m', v', p1 = adam_kernel's sequence on g', rounding for rounding
+//   p  = i inside a noised range ? fmaf(std, nrm(i), p1) : p1,  nrm(i) = normal i % 4 of Philox quad offset + i / 4 under
+//        key seed ^ DIP_SGLD_KEY -- quads are counted from p, so the stream does not depend on the range table
+// One thread per quad per trip of the grid-stride loop: one Philox block serves four elements, and a quad without a noised
+// element draws nothing.  The table {begin, end} x nranges (sorted, disjoint) is staged into LDS once per block; a quad finds
+// the first range that ends behind its first element by binary search and walks on from there element by element.
+// st == NULL / ns == NULL: the by-value scalars (the host-scalar entry point).
+#define DIP_SGLD_MAX_RANGES 512
+#define DIP_SGLD_KEY 0x53474C4453474C44ull
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void adam_sgld_kernel(float* __restrict__ p_, const float* __restrict__ g_,
+                                                        float* __restrict__ m_, float* __restrict__ v_, int64_t n, float w1,
+                                                        float beta2, float omb2, float step_size, float bc2_sqrt, float eps,
+                                                        float wd, const DipIterState* __restrict__ st_,
+                                                        const DipSgldState* __restrict__ ns_, float std, uint64_t seed,
+                                                        uint64_t offset, const int64_t* __restrict__ ranges_, int nranges,
+                                                        const DipGrpArg<GRP> grp) {
+    // Nothing in this body may be contracted into an FMA that is not written as one: adam_kernel's v = v * beta2 + ((1 - beta2)
+    // * g) * g rounds three times, and so must this.  The pragma is lexical and __fmul_rn / __fadd_rn are plain * and + in a
+    // header, outside its reach: the products and sums below are written with the operators themselves.
+#pragma clang fp contract(off)
+    DIP_GRP_PTR(float*, p);
+    DIP_GRP_PTR(const float*, g);
+    DIP_GRP_PTR(float*, m);
+    DIP_GRP_PTR(float*, v);
+    DIP_GRP_PTR(const DipIterState*, st);
+    DIP_GRP_PTR(const DipSgldState*, ns);
+    DIP_GRP_PTR(const int64_t*, ranges);
+    __shared__ int64_t rb[DIP_SGLD_MAX_RANGES], re[DIP_SGLD_MAX_RANGES];
+    for (int r = threadIdx.x; r < nranges; r += 256) {
+        rb[r] = ranges[2 * r];
+        re[r] = ranges[2 * r + 1];
+    }
+    __syncthreads();
+    if (st != nullptr) {
+        step_size = st->step_size;
+        bc2_sqrt = st->bc2_sqrt;
+    }
+    if (ns != nullptr) {
+        offset = ns->offset;
+        seed = ns->seed;
+        std = ns->std;
+    }
+    seed ^= DIP_SGLD_KEY;
+    const float neg_step = -step_size;
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const int64_t quads = (n + 3) / 4;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) {
+        const int64_t i0 = q * 4;
+        const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
+        // first range with end > i0
+        int lo = 0, hi = nranges;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (re[mid] > i0) hi = mid; else lo = mid + 1;
+        }
+        unsigned inside = 0;                      // bit e: element i0 + e is noised
+        for (int e = 0, r = lo; e < cnt; ++e) {
+            while (r < nranges && re[r] <= i0 + e) ++r;
+            if (r < nranges && rb[r] <= i0 + e) inside |= 1u << e;
+        }
+        float nrm[4] = {0.f, 0.f, 0.f, 0.f};
+        if (inside) philox_normals4((uint64_t)q + offset, seed, nrm);
+        float pv[4], gv[4], mv[4], vv[4];
+        const bool whole = vec && cnt == 4;
+        if (whole) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(p + i0), b = *reinterpret_cast<const f32x4*>(g + i0);
+            const f32x4 c = *reinterpret_cast<const f32x4*>(m + i0), d = *reinterpret_cast<const f32x4*>(v + i0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { pv[e] = a[e]; gv[e] = b[e]; mv[e] = c[e]; vv[e] = d[e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (e < cnt) { pv[e] = p[i0 + e]; gv[e] = g[i0 + e]; mv[e] = m[i0 + e]; vv[e] = v[i0 + e]; }
+                else { pv[e] = 0.f; gv[e] = 0.f; mv[e] = 0.f; vv[e] = 0.f; }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gi = wd != 0.f ? fmaf(wd, pv[e], gv[e]) : gv[e];
+            const float mi = fmaf(w1, gi - mv[e], mv[e]);
+            const float vi = vv[e] * beta2 + (omb2 * gi) * gi;
+            const float denom = __fdiv_rn(__fsqrt_rn(vi), bc2_sqrt) + eps;
+            const float p1 = pv[e] + __fdiv_rn(neg_step * mi, denom);
+            pv[e] = (inside >> e) & 1u ? fmaf(std, nrm[e], p1) : p1;
+            mv[e] = mi;
+            vv[e] = vi;
+        }
+        if (whole) {
+            f32x4 a, c, d;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a[e] = pv[e]; c[e] = mv[e]; d[e] = vv[e]; }
+            *reinterpret_cast<f32x4*>(p + i0) = a;
+            *reinterpret_cast<f32x4*>(m + i0) = c;
+            *reinterpret_cast<f32x4*>(v + i0) = d;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (e < cnt) { p[i0 + e] = pv[e]; m[i0 + e] = mv[e]; v[i0 + e] = vv[e]; }
+        }
     }
 }
 
@@ -493,6 +606,57 @@ extern "C" int dip_noise_axpy_dev2(const float* z, float* out, int64_t n, float 
                                   (hipStream_t)stream, z, out, n, sigma, (uint64_t)0, (uint64_t)0, (const uint64_t*)state_dev);
     DIP_CHECK_LAUNCH();
     return dip_counter_add(state_dev, (uint64_t)quads, stream);
+}
+
+namespace {
+// what both SGLD entry points refuse, and the launch they share
+int adam_sgld_launch(const char* who, float* p, const float* g, float* m, float* v, int64_t n, double beta1, double beta2,
+                     double eps, double weight_decay, float step_size, float bc2_sqrt, const DipIterState* st,
+                     const DipSgldState* ns, float std, uint64_t seed, uint64_t offset, const int64_t* ranges, int nranges,
+                     void* stream) {
+    static thread_local char msg[96];
+    const char* why = nullptr;
+    if (p == nullptr || g == nullptr || m == nullptr || v == nullptr) why = "p, g, m or v is NULL";
+    else if (nranges < 0) why = "nranges is negative";
+    else if (nranges > 0 && ranges == nullptr) why = "the range table is NULL";
+    else if (nranges > DIP_SGLD_MAX_RANGES) why = "the range table has more than 512 entries";
+    if (why != nullptr) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, why);
+        DIP_FAIL(msg);
+    }
+    const int64_t quads = (n + 3) / 4;
+    int64_t blocks = (quads + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    dip_launch_pair<DIP_FAM_LOSS>(adam_sgld_kernel<false>, adam_sgld_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
+                                  (hipStream_t)stream, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                                  step_size, bc2_sqrt, (float)eps, (float)weight_decay, st, ns, std, seed, offset, ranges, nranges);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace
+
+// Adam with weight decay + SGLD noise on the noised ranges, host scalars (the relation dip_adam_step has to dip_adam_step_dev)
+extern "C" int dip_adam_sgld_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                                  double eps, double weight_decay, int step, float std, uint64_t seed, uint64_t offset,
+                                  const int64_t* ranges, int nranges, void* stream) {
+    if (n <= 0) return 0;
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    return adam_sgld_launch("adam_sgld_step", p, g, m, v, n, beta1, beta2, eps, weight_decay, (float)(lr / bc1), (float)sqrt(bc2),
+                            nullptr, nullptr, std, seed, offset, ranges, nranges, stream);
+}
+
+// the same with the step scalars read from a DipIterState and {offset, seed, std} from a DipSgldState, whose offset advances
+extern "C" int dip_adam_sgld_step_dev(float* p, const float* g, float* m, float* v, int64_t n, double beta1, double beta2,
+                                      double eps, double weight_decay, const DipIterState* st, DipSgldState* noise,
+                                      const int64_t* ranges, int nranges, void* stream) {
+    if (n <= 0) return 0;
+    if (st == nullptr) DIP_FAIL("adam_sgld_step_dev: iteration state is NULL");
+    if (noise == nullptr) nranges = 0;            // no noise: weight decay only
+    const int rc = adam_sgld_launch("adam_sgld_step_dev", p, g, m, v, n, beta1, beta2, eps, weight_decay, 0.f, 1.f, st,
+                                    nranges > 0 ? noise : nullptr, 0.f, 0, 0, nranges > 0 ? ranges : nullptr, nranges, stream);
+    if (rc != 0 || noise == nullptr) return rc;
+    return dip_counter_add(&noise->offset, (uint64_t)((n + 3) / 4), stream);
 }
 
 extern "C" int dip_lanczos_down_fwd(const float* x, const float* taps, float* y, int C, int H, int W, int k,

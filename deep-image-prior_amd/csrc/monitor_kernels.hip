@@ -148,7 +148,71 @@ __global__ __launch_bounds__(256) void arena_backtrack_kernel(float* __restrict_
     }
 }
 
+// ---------------------------------------------------------------- posterior mean / variance of the outputs (Welford)
+// Iteration i = counter[0] is a sample iff i >= burn_in and (i - burn_in) % every == 0 (and count < 2^24: k stays exact as a
+// float; the host refuses first).  Every block reads counter and count, none writes them: the one-thread kernel behind the
+// element pass advances both, ordered by the stream.
+#define DIP_POSTERIOR_MAX_SAMPLES (1 << 24)
+__device__ __forceinline__ bool posterior_is_sample(int it, int count, int burn_in, int every) {
+    return it >= burn_in && (it - burn_in) % every == 0 && count >= 0 && count < DIP_POSTERIOR_MAX_SAMPLES;
+}
+
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void posterior_update_kernel(const float* __restrict__ out_, float* __restrict__ mean_,
+                                                               float* __restrict__ m2_, int64_t n, int burn_in, int every,
+                                                               const int* __restrict__ counter_, const int* __restrict__ count_,
+                                                               const DipGrpArg<GRP> grp) {
+    // Every operation rounds on its own: without the pragma m2 + d * (x - mean') becomes one FMA.  It is lexical, and
+    // __fmul_rn / __fadd_rn are plain * and + in a header, outside its reach: the operators themselves are written here.
+#pragma clang fp contract(off)
+    DIP_GRP_PTR(const float*, out);
+    DIP_GRP_PTR(float*, mean);
+    DIP_GRP_PTR(float*, m2);
+    DIP_GRP_PTR(const int*, counter);
+    DIP_GRP_PTR(const int*, count);
+    const int it = counter[0], cnt = count[0];    // uniform
+    if (it < 0 || !posterior_is_sample(it, cnt, burn_in, every)) return;
+    const float k = (float)(cnt + 1);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float x = out[i], mu = mean[i];
+        const float d = x - mu;
+        const float mu2 = mu + __fdiv_rn(d, k);
+        mean[i] = mu2;
+        m2[i] = m2[i] + d * (x - mu2);
+    }
+}
+
+template <bool GRP = false>
+__global__ __launch_bounds__(64) void posterior_advance_kernel(int burn_in, int every, int* __restrict__ counter_,
+                                                               int* __restrict__ count_, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(int*, counter);
+    DIP_GRP_PTR(int*, count);
+    if (threadIdx.x != 0) return;
+    const int it = counter[0], cnt = count[0];
+    if (it < 0 || it == 0x7fffffff) return;       // (a counter the host did not initialise)
+    if (posterior_is_sample(it, cnt, burn_in, every)) count[0] = cnt + 1;
+    counter[0] = it + 1;
+}
+
 }  // namespace
+
+extern "C" int dip_posterior_dev(const DipPosteriorDesc* d, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d == nullptr) DIP_FAIL("posterior_dev: NULL descriptor");
+    if (d->out == nullptr || d->mean == nullptr || d->m2 == nullptr || d->count == nullptr || d->counter == nullptr)
+        DIP_FAIL("posterior_dev: a required pointer is NULL");
+    if (d->n <= 0 || d->burn_in < 0 || d->every < 1) DIP_FAIL("posterior_dev: n > 0, burn_in >= 0 and every >= 1 are required");
+    if (d->n > ((int64_t)1 << 33)) DIP_FAIL("posterior_dev: n must be <= 2^33");
+    const int nblk = dip_fit_monitor_nblk(d->n);
+    dip_launch_pair<DIP_FAM_LOSS>(posterior_update_kernel<false>, posterior_update_kernel<true>, dim3(nblk), dim3(256), 0, st,
+                                  d->out, d->mean, d->m2, d->n, d->burn_in, d->every, (const int*)d->counter,
+                                  (const int*)d->count);
+    DIP_CHECK_LAUNCH();
+    dip_launch_pair<DIP_FAM_LOSS>(posterior_advance_kernel<false>, posterior_advance_kernel<true>, dim3(1), dim3(64), 0, st,
+                                  d->burn_in, d->every, d->counter, d->count);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int dip_fit_monitor_nblk(int64_t n) {
     int64_t b = (n + 1023) / 1024;

@@ -95,6 +95,15 @@ state freezes; its fit goes on, because a row cannot leave the launch list.
     mon.best_iter, mon.stopped                  # B ints each; mon.history() [B, iters, 5], mon.best_out [B, C, H, W]
     mon.restore_best()                          # nets[b] carries the parameters of its minimum again (b=: one instance)
 
+SGLD fits (dip_optim.FusedAdam(weight_decay=, noise_std=, noise_seed=) per instance): `weight_decay=`, `param_noise_std=` (one
+float or B floats: a noise-level sweep in one launch list) and `param_noise_seeds=` (default: `seeds`).  With one of them set
+ONE grouped dip_adam_sgld_step_dev takes dip_adam_step_dev's place inside the bracket and the hipGraph, and the DipSgldState
+{offset, seed, std} and the range table of the 4-D parameters are two more rows of the slab, behind everything else; without
+them launch list and slab are what they were.  g.set_param_noise_std(x_or_list) rewrites the levels in stream order.  Every
+instance is bit-identical to its solo NativeIteration fit with the same seeds (tests/test_sgld_fit_gpu.py).
+
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, weight_decay=5e-8, param_noise_std=[1e-4, 2e-4, 4e-4])
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -145,7 +154,7 @@ class GroupedFits:
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
                  ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5,
-                 early_stop=None):
+                 early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
@@ -163,7 +172,11 @@ class GroupedFits:
         weights is refused (an instance with weight 0 on the TV path would differ from its solo fit where s == 0).
         early_stop: None, or a utils.fit_monitor.GroupedEarlyStopMonitor: the ground-truth-free stopping criterion per instance
         ('wmv' or the ring-free 'emv'), inside the launch list behind monitor='s launches and in front of Adam; independent of
-        monitor= and of the group kind (the record needs the net output only).  run_until() polls it."""
+        monitor= and of the group kind (the record needs the net output only).  run_until() polls it.
+        weight_decay / param_noise_std / param_noise_seeds: SGLD fits (dip_optim.FusedAdam(weight_decay=, noise_std=,
+        noise_seed=) per instance): param_noise_std is one float or B floats -- a noise-level sweep in one launch list -- the
+        seeds default to `seeds`.  With one of them set ONE grouped dip_adam_sgld_step_dev takes dip_adam_step_dev's place and
+        two rows join the slab behind everything else: the DipSgldState and the range table of the 4-D parameters."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
@@ -171,6 +184,10 @@ class GroupedFits:
         self.early_stop = self._check_monitor_slot(early_stop, "early_stop")
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
+        self.weight_decay, self.param_noise_std, self.param_noise_seeds = self._check_sgld(
+            weight_decay, param_noise_std, param_noise_seeds, B, [int(s) for s in (seeds if seeds is not None else range(B))])
+        # (explicit zeros are the defaults: the launch list and the slab of a group without SGLD)
+        self.sgld = self.weight_decay != 0.0 or any(s != 0.0 for s in self.param_noise_std) or param_noise_seeds is not None
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
             raise RuntimeError("dip-amd: GroupedFits needs nets built by models.skip.skip()")
@@ -262,6 +279,8 @@ class GroupedFits:
                     if self.tv_weights is not None:
                         self._inst(ex["tv_weight"], b).fill_(self.tv_weights[b])
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
+                    if self.sgld:
+                        self._inst(ex["sgld"], b).copy_(self._sgld_state(b))
             # --- what the caller reads: strided views over the instances
             hr = (oc.Cout, eng.Hout, eng.Wout)
             self.losses = self._strided(ex["loss"])
@@ -361,6 +380,42 @@ class GroupedFits:
             raise ValueError(f"dip-amd: GroupedFits: tv_weights mixes zero and positive weights ({ws}): one launch list serves "
                              "either the TV tail or the plain one; fit the instances without TV in a group of their own")
         return ws, beta
+
+    @staticmethod
+    def _check_sgld(weight_decay, param_noise_std, param_noise_seeds, B, seeds):
+        """(weight_decay, the B noise levels, the B seeds) of an SGLD group, or the ValueError that says what is wrong."""
+        if not float(weight_decay) >= 0.0:                          # (a NaN compares false)
+            raise ValueError(f"dip-amd: GroupedFits: weight_decay must be >= 0, got {weight_decay}")
+        stds = list(param_noise_std) if isinstance(param_noise_std, (list, tuple)) or hasattr(param_noise_std, "__len__") \
+            else [param_noise_std] * B
+        if len(stds) != B:
+            raise ValueError(f"GroupedFits: param_noise_std is one float or one per instance: got {len(stds)} for {B} nets")
+        if any(not float(s) >= 0.0 for s in stds):
+            raise ValueError(f"dip-amd: GroupedFits: param_noise_std must be >= 0, got {stds}")
+        sd = list(seeds) if param_noise_seeds is None else [int(s) for s in param_noise_seeds]
+        if len(sd) != B:
+            raise ValueError(f"GroupedFits: param_noise_seeds holds one seed per instance: got {len(sd)} for {B} nets")
+        return float(weight_decay), [float(s) for s in stds], [s & 0xFFFFFFFFFFFFFFFF for s in sd]
+
+    def _sgld_state(self, b):
+        """Instance b's DipSgldState {offset 0, seed, std} as int64[3] on the host."""
+        s = N.DipSgldState(0, self.param_noise_seeds[b], self.param_noise_std[b], 0.0)
+        return torch.frombuffer(bytearray(bytes(s)), dtype=torch.int64)
+
+    def set_param_noise_std(self, std):
+        """Other noise levels (one float or B floats) for the iterations that follow: FusedAdam.set_noise_std per instance.
+        The device floats are rewritten in stream order; the launch list and a captured hipGraph stay as they are."""
+        if not self.sgld:
+            raise ValueError("dip-amd: GroupedFits.set_param_noise_std on a group without SGLD: construct it with "
+                             "param_noise_std= / weight_decay=")
+        _, stds, _ = self._check_sgld(self.weight_decay, std, self.param_noise_seeds, self.B, self.seeds)
+        for b, s in enumerate(stds):
+            self._inst(self._row0_extra["sgld"], b).view(torch.float32)[4:5].fill_(s)
+        self.param_noise_std = stds
+
+    def param_noise_offsets(self):
+        """The Philox offset of every instance's SGLD stream, as the device holds it."""
+        return [int(self._inst(self._row0_extra["sgld"], b)[0].item()) & 0xFFFFFFFFFFFFFFFF for b in range(self.B)]
 
     def set_tv_weights(self, tv_weights):
         """Other positive weights for the iterations that follow (SRHead.set_tv_weight per instance): the device scalars are
@@ -514,6 +569,22 @@ class GroupedFits:
             d, launches = self._carve_monitor(slab, m, prefix)
             setattr(self, desc, d)
             setattr(self, ops, launches)
+        if self.sgld:
+            # behind everything else: the DipSgldState and the range table of the 4-D parameters (dip_optim.noise_ranges: what
+            # a solo FusedAdam over the net's parameters noises), and the extent a solo FusedAdam group steps
+            import dip_optim
+            plist = eng.param_list
+            self._sgld_ranges = dip_optim.noise_ranges(plist, eng.slots, [p for p in plist if p.dim() == 4])
+            if len(self._sgld_ranges) > dip_optim.SGLD_MAX_RANGES:
+                raise RuntimeError(f"dip-amd: GroupedFits: {len(self._sgld_ranges)} noised ranges; dip_adam_sgld_step_dev takes at "
+                                   f"most {dip_optim.SGLD_MAX_RANGES}")
+            self._sgld_n = eng.slots[-1] + plist[-1].numel()
+            ex["sgld"] = slab.alloc(3, torch.int64, zero=True)
+            ex["sgld_ranges"] = slab.alloc(max(2 * len(self._sgld_ranges), 1), torch.int64, zero=True)
+            ex["sgld"].copy_(self._sgld_state(0))
+            if self._sgld_ranges:
+                ex["sgld_ranges"][:2 * len(self._sgld_ranges)].copy_(
+                    torch.tensor(self._sgld_ranges, dtype=torch.int64).reshape(-1))
 
     def _monitor_sizes(self, m):
         from utils.fit_monitor import monitor_sizes
@@ -628,9 +699,16 @@ class GroupedFits:
                     N.check(fn(*args, st), name)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
             N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")
-            N.check(lib.dip_adam_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(), ex["v"].data_ptr(),
-                                          eng.n_arena, self.ADAM_BETAS[0], self.ADAM_BETAS[1], self.ADAM_EPS,
-                                          ex["iter"].data_ptr(), st), "adam_step_dev")
+            if self.sgld:                   # FusedAdam(weight_decay=, noise_std=, noise_seed=) per instance, ONE launch
+                N.check(lib.dip_adam_sgld_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(),
+                                                   ex["v"].data_ptr(), self._sgld_n, self.ADAM_BETAS[0], self.ADAM_BETAS[1],
+                                                   self.ADAM_EPS, self.weight_decay, ex["iter"].data_ptr(),
+                                                   ex["sgld"].data_ptr(), ex["sgld_ranges"].data_ptr(),
+                                                   len(self._sgld_ranges), st), "adam_sgld_step_dev")
+            else:
+                N.check(lib.dip_adam_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(),
+                                              ex["v"].data_ptr(), eng.n_arena, self.ADAM_BETAS[0], self.ADAM_BETAS[1],
+                                              self.ADAM_EPS, ex["iter"].data_ptr(), st), "adam_step_dev")
         finally:
             lib.dip_group_end()
         # ATen, batched over the instances: BatchNorm's num_batches_tracked and the closure's out_avg

@@ -155,6 +155,16 @@ class DipEarlyStopEmvDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class DipSgldState(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("seed", C.c_uint64), ("std", C.c_float), ("pad_", C.c_float)]
+
+
+class DipPosteriorDesc(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("mean", C.c_void_p), ("m2", C.c_void_p), ("count", C.c_void_p), ("counter", C.c_void_p),
+                ("n", C.c_int64), ("burn_in", C.c_int32), ("every", C.c_int32)]
+
+
+assert C.sizeof(DipSgldState) == 24 and C.sizeof(DipPosteriorDesc) == 56                 # include/dip_hip.h states both
 assert C.sizeof(DipEarlyStopDesc) == 96 and C.sizeof(DipEarlyStopEmvDesc) == 88          # include/dip_hip.h states both
 
 _SIGS = {
@@ -310,6 +320,12 @@ _SIGS = {
     "dip_early_stop_dev": (C.c_int, [C.POINTER(DipEarlyStopDesc), C.c_void_p]),
     "dip_early_stop_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dip_early_stop_emv_dev": (C.c_int, [C.POINTER(DipEarlyStopEmvDesc), C.c_void_p]),
+    "dip_adam_sgld_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_double, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
+                                     C.c_void_p, C.c_int, C.c_void_p]),
+    "dip_adam_sgld_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dip_posterior_dev": (C.c_int, [C.POINTER(DipPosteriorDesc), C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p]),
     "dip_lanczos_down_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -59,14 +59,95 @@ def _split_contiguous(params, max_gap=4):
     return groups
 
 
+def noise_ranges(params, offsets, noised):
+    """The range table of a contiguous group: the [begin, end) extents, in elements from the group's base, of the parameters
+    that are in `noised` (by identity), merged where adjacent.  Sorted and disjoint; an alignment gap is never inside one."""
+    ids = {id(p) for p in noised}
+    out = []
+    for p, o in zip(params, offsets):
+        if id(p) not in ids:
+            continue
+        if out and out[-1][1] == o:
+            out[-1][1] = o + p.numel()
+        else:
+            out.append([o, o + p.numel()])
+    return [tuple(r) for r in out]
+
+
+SGLD_MAX_RANGES = 512                          # (the LDS table of adam_sgld_kernel, csrc/misc_kernels.hip)
+
+
 class FusedAdam:
-    def __init__(self, parameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    """torch.optim.Adam over flat arenas (module docstring), and with weight_decay / noise_std the SGLD sampler of Cheng et
+    al., "A Bayesian Perspective on the Deep Image Prior" (CVPR 2019) in the same launch (dip_adam_sgld_step_dev):
+
+        weight_decay   torch.optim.Adam's: g <- g + weight_decay * p in front of the moments (the Gaussian prior)
+        noise_std      after the step, p <- p + noise_std * N(0, 1) on the noised parameters; set_noise_std(x) changes it
+                       between steps without a re-plan (one 4-byte write on the current stream)
+        noise_seed     the seed of the Philox stream (key noise_seed ^ 0x53474C4453474C44: a RegNoise of the same seed draws
+                       other normals); contiguous group j of the list starts at offset j << 48
+        noise_params   None: every parameter of the list with dim() == 4 -- the convolution weights, what the paper's code
+                       perturbs.  Otherwise an iterable of parameters of the list (by identity).  With get_params('net,input',
+                       ...) the net input is 4-D too: pass the explicit list then.
+
+    With weight_decay == 0 and noise_std == 0 at construction the optimiser issues what it always issued (dip_adam_tick +
+    dip_adam_step_dev); otherwise dip_adam_tick + dip_adam_sgld_step_dev, also after set_noise_std(0): the stream keeps
+    advancing.  Everything that varies per step is in device memory, so GraphedIteration captures the step as it is."""
+
+    def __init__(self, parameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, noise_std=0.0, noise_seed=0,
+                 noise_params=None):
         self.params = [p for p in parameters]
         self.lr, self.betas, self.eps = lr, betas, eps
+        if not float(weight_decay) >= 0.0:                          # (a NaN compares false)
+            raise ValueError(f"dip-amd: FusedAdam: weight_decay must be >= 0, got {weight_decay}")
+        if not float(noise_std) >= 0.0:
+            raise ValueError(f"dip-amd: FusedAdam: noise_std must be >= 0, got {noise_std}")
+        self.weight_decay, self.noise_std = float(weight_decay), float(noise_std)
+        self.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+        self.sgld = self.weight_decay != 0.0 or self.noise_std != 0.0      # which entry point step() issues: fixed here
+        if noise_params is None:
+            self.noise_params = [p for p in self.params if p.dim() == 4]
+        else:
+            self.noise_params = list(noise_params)
+            mine = {id(p) for p in self.params}
+            if any(id(p) not in mine for p in self.noise_params):
+                raise ValueError("dip-amd: FusedAdam: noise_params holds a parameter that is not in the optimiser's list")
         self.step_count = 0
         self._groups = None
         self._sig = None
         self._iter_state = {}                  # device -> DipIterState bytes (uint8[16])
+
+    def set_noise_std(self, std):
+        """The noise level from the next step on: written into every group's DipSgldState on the current stream.  No re-plan
+        (NativeIteration keeps its command arrays), so it can be annealed between run() calls."""
+        if not float(std) >= 0.0:
+            raise ValueError(f"dip-amd: FusedAdam.set_noise_std: noise_std must be >= 0, got {std}")
+        if not self.sgld:
+            raise RuntimeError("dip-amd: FusedAdam.set_noise_std: this optimiser was constructed without weight_decay / noise_std "
+                               "and issues the plain Adam entry point; construct it with noise_std > 0")
+        self.noise_std = float(std)
+        for g in self._groups or ():
+            g.sgld.view(torch.float32)[4:5].fill_(self.noise_std)
+
+    def _init_sgld(self, g, j, old):
+        """Group j's DipSgldState {offset = j << 48, seed, std} and range table in device memory (`old`: the state of the group
+        that started at the same parameter before the parameters moved -- the stream goes on where it was)."""
+        dev = g.params[0].device
+        g.ranges = noise_ranges(g.params, g.offsets, self.noise_params)
+        if len(g.ranges) > SGLD_MAX_RANGES:
+            raise RuntimeError(f"dip-amd: FusedAdam: {len(g.ranges)} noised ranges in one contiguous group; "
+                               f"dip_adam_sgld_step_dev takes at most {SGLD_MAX_RANGES}")
+        if old is not None:
+            g.sgld = old.to(dev)
+        else:
+            s = N.DipSgldState((j << 48) & 0xFFFFFFFFFFFFFFFF, self.noise_seed, self.noise_std, 0.0)
+            g.sgld = torch.frombuffer(bytearray(bytes(s)), dtype=torch.int64).to(dev)        # int64[3]: 8-byte aligned
+        g.sgld.view(torch.float32)[4:5].fill_(self.noise_std)
+        g.range_table = torch.tensor(g.ranges, dtype=torch.int64).reshape(-1, 2).to(dev) if g.ranges else None
+
+    def device_noise_offset(self, j=0):
+        """The Philox offset of contiguous group j as the device holds it (synchronises)."""
+        return int(self._groups[j].sgld[0].item()) & 0xFFFFFFFFFFFFFFFF
 
     # torch.optim API subset used by optimize() and the notebooks
     def zero_grad(self, set_to_none: bool = True):
@@ -89,17 +170,21 @@ class FusedAdam:
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("dip-amd FusedAdam: parameters must be contiguous fp32 CUDA tensors "
                                    f"(got {p.dtype} on {p.device}); this backend has no CPU optimiser path")
-        old = {}
+        old, old_sgld = {}, {}
         if self._groups is not None:          # parameters moved (net re-typed): carry the moments over
             for g in self._groups:
                 for p, o in zip(g.params, g.offsets):
                     old[id(p)] = (g.m[o:o + p.numel()].clone(), g.v[o:o + p.numel()].clone())
+                if self.sgld:
+                    old_sgld[id(g.params[0])] = g.sgld
         self._groups = [_Group(run) for run in _split_contiguous(self.params)]
-        for g in self._groups:
+        for j, g in enumerate(self._groups):
             for p, o in zip(g.params, g.offsets):
                 if id(p) in old:
                     g.m[o:o + p.numel()].copy_(old[id(p)][0])
                     g.v[o:o + p.numel()].copy_(old[id(p)][1])
+            if self.sgld:
+                self._init_sgld(g, j, old_sgld.get(id(g.params[0])))
         self._sig = self._signature()
 
     @torch.no_grad()
@@ -146,10 +231,27 @@ class FusedAdam:
                     N.check(lib.dip_adam_tick(st.data_ptr(), float(self.lr), float(self.betas[0]),
                                               float(self.betas[1]), stream), "adam_tick")
                     ticked.add(dev)
-                N.check(lib.dip_adam_step_dev(g.base, flat_ptr, g.m.data_ptr(), g.v.data_ptr(), g.numel,
-                                              float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                              st.data_ptr(), stream), "adam_step_dev")
+                fn, args, name = self._step_launch(lib, g, flat_ptr, st)
+                N.check(fn(*args, stream), name)
         return loss
+
+    def _step_launch(self, lib, g, grad_ptr, st):
+        """(fn, args without the stream, name) of group g's update: what step() issues and NativeIteration's Adam phase holds."""
+        b1, b2, eps = float(self.betas[0]), float(self.betas[1]), float(self.eps)
+        if not self.sgld:
+            return (lib.dip_adam_step_dev, (g.base, grad_ptr, g.m.data_ptr(), g.v.data_ptr(), g.numel, b1, b2, eps,
+                                            st.data_ptr()), "adam_step_dev")
+        return (lib.dip_adam_sgld_step_dev, (g.base, grad_ptr, g.m.data_ptr(), g.v.data_ptr(), g.numel, b1, b2, eps,
+                                             self.weight_decay, st.data_ptr(), g.sgld.data_ptr(),
+                                             None if g.range_table is None else g.range_table.data_ptr(), len(g.ranges)),
+                "adam_sgld_step_dev")
+
+    def _plan_key(self):
+        """What NativeIteration's Adam phase was built from; with the defaults, what it always was."""
+        key = (self.lr, self.betas, self.eps, id(self._groups))
+        if self.sgld:
+            key += (self.weight_decay, tuple((id(g.sgld), id(g.range_table), tuple(g.ranges)) for g in self._groups or ()))
+        return key
 
     def _state(self, dev, step):
         """The DipIterState of device `dev`; created holding `step` (the count before the step about to be taken)."""
@@ -379,9 +481,24 @@ class NativeIteration:
         es = EarlyStopMonitor(img_noisy, window=100, patience=1000, net=net, capacity=num_iter)
         it = NativeIteration(net, head, opt, net_input, reg_noise=reg, early_stop=es)
         issued, losses = it.run_until(num_iter, check_every=50)      # polls the 4-byte `stopped` word once per 50 iterations
-        es.best_iter, es.best_out; es.restore_best()"""
+        es.best_iter, es.best_out; es.restore_best()
 
-    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None, early_stop=None):
+    An SGLD optimiser -- FusedAdam(..., weight_decay=, noise_std=, noise_seed=) -- is accepted as it is: the Adam phase then holds
+    dip_adam_sgld_step_dev instead of dip_adam_step_dev, on the DipSgldState the eager opt.step() uses, so the two forms still
+    alternate bit-identically; opt.set_noise_std(x) between run() calls needs no re-plan.  The plan's key gains the new fields only
+    for such an optimiser.
+
+    posterior=PosteriorMonitor(img_like, burn_in, every) is a third keyword, independent of the other two: the sample mean and
+    variance of the outputs (utils.fit_monitor) as one more command array, dip_posterior_dev, behind monitor= and early_stop= and
+    in front of Adam -- where `pm.update(out)` stands in the eager closure, so a sample is the output of the parameters that are
+    about to be stepped and perturbed.  It does not touch the fit; with posterior=None the plan's key is what it was.
+
+        opt = FusedAdam(get_params('net', net, net_input), lr=LR, weight_decay=5e-8, noise_std=1e-4, noise_seed=0)
+        pm = PosteriorMonitor(img_noisy, burn_in=7000, every=50)
+        it = NativeIteration(net, head, opt, net_input, reg_noise=reg, posterior=pm)
+        it.run(num_iter); pm.mean, pm.variance(), pm.count"""
+
+    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None, early_stop=None, posterior=None):
         import dip_group
         from utils.loss_head import MSEHead, SRHead
         from utils.reg_noise import RegNoise
@@ -404,7 +521,7 @@ class NativeIteration:
                              "opt_over with 'input' or 'down' goes through the eager closure")
         # (the monitor's type is refused before the first check that needs a GPU)
         self.monitor, self.device = monitor, getattr(net_input, "device", None)
-        self.early_stop = early_stop
+        self.early_stop, self.posterior = early_stop, posterior
         self._check_monitors()
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
@@ -446,9 +563,9 @@ class NativeIteration:
             raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
 
     def _monitors(self):
-        """The monitors of this iteration in launch order -- monitor=, then early_stop=, both in front of Adam -- as (slot,
-        monitor) pairs."""
-        return [(slot, getattr(self, slot)) for slot in ("monitor", "early_stop") if getattr(self, slot) is not None]
+        """The monitors of this iteration in launch order -- monitor=, then early_stop=, then posterior=, all in front of Adam
+        -- as (slot, monitor) pairs."""
+        return [(slot, getattr(self, slot)) for slot in ("monitor", "early_stop", "posterior") if getattr(self, slot) is not None]
 
     def _check_monitors(self):
         """What can be said about monitor= and early_stop= before the output size is known (the image shape: _build)."""
@@ -456,7 +573,9 @@ class NativeIteration:
         takes = {"monitor": ((FM.FitMonitor, FM.SRFitMonitor, FM.RestorationFitMonitor), "dip-amd: monitor must be a "
                              "utils.fit_monitor.FitMonitor, an SRFitMonitor, a RestorationFitMonitor or None", "back-tracks"),
                  "early_stop": (FM.EarlyStopMonitor, "dip-amd: early_stop must be a utils.fit_monitor.EarlyStopMonitor or None",
-                                "keeps the parameters of")}
+                                "keeps the parameters of"),
+                 "posterior": (FM.PosteriorMonitor, "dip-amd: posterior must be a utils.fit_monitor.PosteriorMonitor or None",
+                               "samples")}
         head = getattr(self, "head", None)
         for slot, m in self._monitors():
             types, refusal, copies = takes[slot]
@@ -477,7 +596,7 @@ class NativeIteration:
         eng, head, opt, reg = self.engine, self.head, self.opt, self.reg
         # (an engine that has never planned has no op lists yet: None never equals a built key)
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
-                opt.lr, opt.betas, opt.eps, id(opt._groups),
+                *opt._plan_key(),
                 head._plan_key(),
                 None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
             + tuple((slot, m._plan_key()) for slot, m in self._monitors())       # (no monitors: the key as it was)
@@ -516,8 +635,8 @@ class NativeIteration:
             if g.params[0].device != dev or g.base < pbase or g.base + 4 * g.numel > pbase + 4 * eng.params.numel():
                 raise RuntimeError("dip-amd: a FusedAdam group lies outside the net's parameter arena")
             # the gradient arena mirrors the parameter arena: the group's gradients are flat at the same offset
-            adam.append((lib.dip_adam_step_dev, (g.base, gbase + (g.base - pbase), g.m.data_ptr(), g.v.data_ptr(), g.numel,
-                                                 b1, b2, float(opt.eps), st.data_ptr()), "adam_step_dev"))
+            # (an SGLD optimiser: dip_adam_sgld_step_dev on the DipSgldState the eager opt.step() uses)
+            adam.append(opt._step_launch(lib, g, gbase + (g.base - pbase), st))
         on_main = lambda ops: N.CmdList([("launch", fn, args, 0, name) for fn, args, name in ops])
         phases = [on_main(pre), fwd, on_main(mid), bwd, on_main(adam)]
         # monitor.update()'s place in stream order: after backward(), before opt.step() -- a fall-back overwrites the parameters

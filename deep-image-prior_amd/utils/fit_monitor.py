@@ -16,6 +16,9 @@ the host reads the record table when it wants to print.
                            variance of the output, keep the minimum's output and parameters.  'wmv' (dip_early_stop_dev): over
                            a ring of the last `window` outputs, 4 * window * n bytes; 'emv' (dip_early_stop_emv_dev): the
                            exponential form, no ring.  Columns var, var_min, best_iter, wait, stopped
+    PosteriorMonitor       no notebook has it either: the sample mean and variance of the outputs of an SGLD fit (Cheng et al.,
+                           "A Bayesian Perspective on the Deep Image Prior"; dip_optim.FusedAdam(noise_std=)) after a burn-in,
+                           dip_posterior_dev.  No record table: mean, variance(), count.  Solo only
 
 In the eager closure, after backward():
 
@@ -119,6 +122,10 @@ EARLY_STOP_BUFFERS = (Buf("ring", lambda z: z.window * z.n, lambda z: (z.window,
                       _COUNTER,
                       Buf("best_out", lambda z: z.n, lambda z: z.img, init="zero"),
                       Buf("best_params", lambda z: z.n_arena, init="zero", when=lambda m: m.keep_params, lazy=True))
+POSTERIOR_BUFFERS = (Buf("mean", lambda z: z.n, lambda z: z.img, init="zero"),
+                     Buf("m2", lambda z: z.n, lambda z: z.img, init="zero"),
+                     Buf("samples", lambda z: 1, lambda z: z.one, _I32, "zero"),          # the descriptor's `count`
+                     _COUNTER)
 
 
 # ---------------------------------------------------------------- descriptors and launches
@@ -159,9 +166,15 @@ def early_stop_emv_descriptor(m, t):
                                  t["out"].numel(), m.alpha, m.warmup, m.patience, m.capacity, 0)
 
 
+def posterior_descriptor(m, t):
+    """DipPosteriorDesc of monitor m (burn_in, every): mean, m2, the sample count and the iteration counter."""
+    p = lambda k: _ptr(t.get(k))
+    return N.DipPosteriorDesc(p("out"), p("mean"), p("m2"), p("samples"), p("counter"), t["out"].numel(), m.burn_in, m.every)
+
+
 _ENTRY = {N.DipFitMonitorDesc: "fit_monitor_dev", N.DipSRMonitorDesc: "sr_monitor_dev",
           N.DipRestoreMonitorDesc: "restore_monitor_dev", N.DipEarlyStopDesc: "early_stop_dev",
-          N.DipEarlyStopEmvDesc: "early_stop_emv_dev"}
+          N.DipEarlyStopEmvDesc: "early_stop_emv_dev", N.DipPosteriorDesc: "posterior_dev"}
 
 
 def monitor_launches(lib, desc, params_ptr=None, n_arena=0, arena_ptr=None):
@@ -257,6 +270,12 @@ class _EarlyStopKind:
         """Device memory the monitor holds, per instance times B ('wmv': the ring dominates, 4 * window * n; 'emv' has none)."""
         self._table()
         return sum(t.numel() * t.element_size() for t in self._buffers() if t is not None)
+
+
+class _PosteriorKind:
+    COLUMNS = ()                                                    # no record table: mean, m2 and the sample count
+    BUFFERS, ARENA, _descriptor = POSTERIOR_BUFFERS, None, posterior_descriptor
+    head_kind = None
 
 
 class _Records:
@@ -654,6 +673,89 @@ class EarlyStopMonitor(_EarlyStopKind, _DeviceRecords):
                              "(no CPU fallback)")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("dip-amd: EarlyStopMonitor.update cannot be captured into a hipGraph (the row index is "
+                               "host-synchronised state)")
+
+    def _issue(self, outs, lptr, stream):
+        self._sync_counter()
+        for fn, args, name in self._launches(self._dev_descriptor(outs[0])):
+            N.check(fn(*args, stream), name)
+
+    def _check_plan(self, out, head):
+        self._check_out(out.shape, "NativeIteration")
+
+
+class PosteriorMonitor(_PosteriorKind, _DeviceRecords):
+    """Sample mean and variance of the net outputs of an SGLD fit (dip_optim.FusedAdam(noise_std=...); Cheng et al., "A Bayesian
+    Perspective on the Deep Image Prior") on the device: iteration i is a sample iff i >= burn_in and (i - burn_in) % every == 0,
+    and a sample updates `mean` and `m2` ([1,C,H,W] fp32, zero before the first) by Welford's rule in individually rounded fp32
+    operations (dip_posterior_dev; include/dip_hip.h states them).  `mean` is the posterior-mean estimate, variance() = m2 /
+    (count - 1) the per-pixel uncertainty map.  No record table: history() / last() do not apply.
+
+    `img_like` gives the shape [1,C,H,W] and the device of the output.  update(out) is the eager form -- after backward() and
+    before the optimiser's step, so the sample is the output of the parameters that are about to be stepped and perturbed --
+    and NativeIteration(posterior=this) issues the same entry point in the same place; the two may alternate.  At most 2**24
+    samples (the count is a float in the update): what would pass it is refused before anything is issued.  Solo only: there
+    is no grouped form yet (the buffers are declared in POSTERIOR_BUFFERS like every other kind's)."""
+    SETTINGS = ("burn_in", "every", "n")
+    MAX_SAMPLES = 2 ** 24
+    _recorded = _DeviceRecords._advance            # update() goes through the device-indexed entry point: the counter moves
+
+    def __init__(self, img_like, burn_in, every=1):
+        # (what needs no GPU is refused first: the type, the settings)
+        if not isinstance(img_like, torch.Tensor):
+            raise TypeError("dip-amd: PosteriorMonitor: img_like is a tensor shaped like the net output ([1,C,H,W])")
+        if int(burn_in) < 0:
+            raise ValueError(f"dip-amd: PosteriorMonitor: burn_in must be >= 0, got {burn_in}")
+        if int(every) < 1:
+            raise ValueError(f"dip-amd: PosteriorMonitor: every must be >= 1, got {every}")
+        self.burn_in, self.every = int(burn_in), int(every)
+        if not img_like.is_cuda:
+            raise RuntimeError("dip-amd: PosteriorMonitor works on MI355X tensors only (no CPU fallback)")
+        self.shape, self.n = tuple(img_like.shape), img_like.numel()
+        if self.n < 1:
+            raise ValueError("dip-amd: PosteriorMonitor: img_like is empty")
+        self._init_device(img_like.device, 2 ** 31 - 1, self.shape, n=self.n)      # (capacity: the int32 iteration index)
+
+    def samples_after(self, i):
+        """How many of the iterations [0, i) are samples."""
+        return 0 if i <= self.burn_in else (i - self.burn_in - 1) // self.every + 1
+
+    def _check_room(self, n):
+        """Refuses n more iterations when they would pass the sample cap (or the int32 index): before anything is issued."""
+        if self.samples_after(self.i + int(n)) > self.MAX_SAMPLES or self.i + int(n) > self.capacity:
+            raise RuntimeError(f"dip-amd: PosteriorMonitor: {int(n)} more iteration(s) after {self.i} would pass the cap of "
+                               f"2**24 samples (burn_in {self.burn_in}, every {self.every}); sample less often")
+
+    def _table(self, need=0):
+        raise RuntimeError("dip-amd: PosteriorMonitor keeps no record table (read mean, variance() and count)")
+
+    @property
+    def count(self):
+        """Samples taken so far (reads one value; synchronises)."""
+        return int(self.samples.item())
+
+    def variance(self):
+        """The sample variance of the outputs per element, m2 / (count - 1), [1,C,H,W]; synchronises."""
+        k = self.count
+        if k < 2:
+            raise RuntimeError(f"dip-amd: PosteriorMonitor.variance needs at least two samples, {k} taken so far")
+        return self.m2 / float(k - 1)
+
+    def _check_out(self, shape, who):
+        if tuple(shape) != self.shape:
+            raise ValueError(f"dip-amd: {who}: the PosteriorMonitor was built for {self.shape}, the net output is {tuple(shape)}")
+
+    def update(self, out):
+        """Call once per closure evaluation, after backward() and before the optimiser's step."""
+        self._update((out,))
+
+    def _check_update(self, o):
+        self._check_out(o.shape, "PosteriorMonitor.update")
+        if not o.is_cuda or o.device != self.dev:
+            raise ValueError(f"dip-amd: PosteriorMonitor.update: the output is on {o.device}, the monitor lives on {self.dev} "
+                             "(no CPU fallback)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dip-amd: PosteriorMonitor.update cannot be captured into a hipGraph (the iteration index is "
                                "host-synchronised state)")
 
     def _issue(self, outs, lptr, stream):

@@ -594,6 +594,41 @@ int dip_counter_add(uint64_t* counter, uint64_t inc, void* stream);
  * (models/common.py:82,95 through torch.nn.BatchNorm2d.forward), whose counters the engine keeps in one int64 arena. */
 int dip_counter_add_n(uint64_t* counters, int n, uint64_t inc, void* stream);
 
+/* ---------------------------------------------------------------- SGLD: Adam + weight decay + parameter noise ---- */
+/* Langevin sampling of the weights (Cheng et al., "A Bayesian Perspective on the Deep Image Prior", CVPR 2019): after the
+ * optimiser step Gaussian noise is added to the convolution weights, with a small weight decay as the Gaussian prior.  ONE
+ * launch over a flat arena does the Adam update with optional weight decay and adds Philox noise to the elements inside a
+ * table of noised ranges.  Per element i of p, with wd = (float)weight_decay:
+ *   g'  = wd != 0 ? fmaf(wd, p[i], g[i]) : g[i]     one rounding, what ATen's CPU grad.add(param, alpha=wd) computes; with
+ *                                                   weight_decay == 0 the fma is skipped: g' = g bit for bit, -0.0 included
+ *   m', v', p1 = the sequence of dip_adam_step on g', rounding for rounding
+ *   p[i] = i inside a noised range ? fmaf(std, nrm(i), p1) : p1
+ * nrm(i) is normal number i % 4 of Philox quad offset + i / 4 of the reg-noise stream (DESIGN.md "The reg-noise stream")
+ * under key seed ^ 0x53474C4453474C44 ("SGLDSGLD"): without the XOR a RegNoise(seed=0) and an SGLD stream of seed 0 would add
+ * the SAME normals to the input and to the first weights.  Quads are indexed from p, not from a range start, so the stream
+ * does not depend on the table; the normals of elements outside the ranges are dropped.
+ * ranges: nranges x {begin, end} int64 in DEVICE memory, in elements of p, sorted and disjoint, at most 512 of them; what lies
+ * beyond n is ignored.  _dev reads step_size / bc2_sqrt from `st` (dip_adam_tick first) and offset / seed / std from *noise, and
+ * advances noise->offset by ceil(n / 4) behind the launch, the way dip_noise_axpy_dev2 advances its counter: a static launch.
+ * n <= 0 returns 0 and launches nothing.  noise == NULL or nranges == 0: no noise, weight decay only (a non-NULL noise still
+ * advances).  NULL p / g / m / v / st with n > 0, ranges == NULL with nranges > 0 (and a noise state), nranges < 0 or > 512:
+ * -1 before anything is launched.  Kernel: one thread per quad per trip of a grid-stride loop (one Philox block serves four
+ * elements), 16-byte loads and stores when all four pointers are 16-byte aligned and the quad is whole, element by element
+ * otherwise; the table is staged into LDS once per block, binary search per quad.  Grouped instantiation: DIP_FAM_LOSS. */
+typedef struct DipSgldState {
+    uint64_t offset;      /* Philox quad of element 0 of the next launch */
+    uint64_t seed;
+    float std;            /* standard deviation of the noise added to a noised element */
+    float pad_;
+} DipSgldState;           /* 24 bytes, device memory */
+int dip_adam_sgld_step_dev(float* p, const float* g, float* m, float* v, int64_t n, double beta1, double beta2, double eps,
+                           double weight_decay, const DipIterState* st, DipSgldState* noise, const int64_t* ranges,
+                           int nranges, void* stream);
+/* The same with host scalars (the relation dip_adam_step has to dip_adam_step_dev): nothing is advanced. */
+int dip_adam_sgld_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, int step, float std, uint64_t seed, uint64_t offset,
+                       const int64_t* ranges, int nranges, void* stream);
+
 /* ---------------------------------------------------------------- fused loss head ------------ */
 /* The tail of the closure in two launches: output conv (1x1, Cout <= 4, weights straight from the
  * OIHW parameter arena) + nn.Sigmoid (models/skip.py:96-98) + optional mask + torch.nn.MSELoss
@@ -925,6 +960,27 @@ typedef struct DipEarlyStopEmvDesc {
     int warmup, patience, capacity, reserved;
 } DipEarlyStopEmvDesc;
 int dip_early_stop_emv_dev(const DipEarlyStopEmvDesc* d, void* stream);
+
+/* Sample mean and variance of the network outputs of an SGLD fit (Welford).  Iteration i = counter[0] is a sample iff
+ * i >= burn_in and (i - burn_in) % every == 0.  Then, per element, with k = (float)(count + 1), every operation individually
+ * rounded in fp32 and nothing contracted:
+ *   d = x - mean;  mean' = mean + d / k;  m2' = m2 + d * (x - mean')
+ * (mean and m2 start at zero; the first sample needs no special case: mean' == x and m2' == 0 exactly).  The sample variance is
+ * m2 / (count - 1).  Two launches: the element pass (256 threads, grid-stride, dip_fit_monitor_nblk(n) blocks) only READS
+ * counter and count; one thread behind it, ordered by the stream, does count += 1 (on a sample) and counter += 1.
+ * Deterministic, no float atomics, nothing synchronises.  count >= 2^24 takes no more samples (k would no longer be exact;
+ * the host refuses first).  Every pointer is required; n in (0, 2^33], burn_in >= 0, every >= 1, otherwise -1 before anything
+ * is launched.  sizeof(DipPosteriorDesc) == 56 (LP64).  Grouped instantiations: family DIP_FAM_LOSS. */
+typedef struct DipPosteriorDesc {
+    const float* out;       /* [n] the network output of this iteration */
+    float* mean;            /* [n] */
+    float* m2;              /* [n] sum of squared deviations */
+    int* count;             /* int32[1]: samples taken */
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    int64_t n;
+    int burn_in, every;
+} DipPosteriorDesc;
+int dip_posterior_dev(const DipPosteriorDesc* d, void* stream);
 
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
