@@ -58,6 +58,7 @@ const Entry g_fns[] = {
     DIP_REG(dip_fit_monitor), DIP_REG(dip_fit_monitor_dev), DIP_REG(dip_arena_backtrack),
     DIP_REG(dip_sr_monitor), DIP_REG(dip_sr_monitor_dev), DIP_REG(dip_restore_monitor), DIP_REG(dip_restore_monitor_dev),
     DIP_REG(dip_early_stop_dev), DIP_REG(dip_early_stop_keep), DIP_REG(dip_early_stop_emv_dev),
+    DIP_REG(dip_ssim_dev),
     DIP_REG(dip_lanczos_down_fwd), DIP_REG(dip_lanczos_down_bwd), DIP_REG(dip_down_dense_fwd), DIP_REG(dip_down_dense_bwd_data),
     DIP_REG(dip_down_dense_bwd_weight), DIP_REG(dip_res_join_fwd), DIP_REG(dip_res_join_bwd),
 };

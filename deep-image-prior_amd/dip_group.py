@@ -95,6 +95,18 @@ state freezes; its fit goes on, because a row cannot leave the launch list.
     mon.best_iter, mon.stopped                  # B ints each; mon.history() [B, iters, 5], mon.best_out [B, C, H, W]
     mon.restore_best()                          # nets[b] carries the parameters of its minimum again (b=: one instance)
 
+The mean structural similarity of every instance's output against its ground truth: `ssim=utils.fit_monitor.GroupedSSIMMonitor(
+imgs_gt, with_avg=False)`, a third keyword for all three group kinds (a super-resolution group: imgs_gt are the HR images).  Its
+buffers -- the ground truth, the partials, the records, the counter -- are per-instance data of the slab behind the es_ rows; ONE
+dip_ssim_dev call inside the group bracket, behind the monitor= and early_stop= launches and in front of Adam, serves all B inside
+the ONE hipGraph of capture(), and instance b's records are those of the solo NativeIteration(ssim=SSIMMonitor(...)) fit, bit for
+bit (tests/test_ssim_gpu.py).  with_avg=True also records the SSIM of the smoothed output: it reads the out_avg rows of
+monitor=GroupedFitMonitor(...).
+
+    sm = GroupedSSIMMonitor(imgs_gt, capacity=num_iter)
+    g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, ssim=sm)
+    g.capture(); g.run(num_iter - 3); sm.history()         # [B, iters, 2]: ssim, ssim_sm
+
 SGLD fits (dip_optim.FusedAdam(weight_decay=, noise_std=, noise_seed=) per instance): `weight_decay=`, `param_noise_std=` (one
 float or B floats: a noise-level sweep in one launch list) and `param_noise_seeds=` (default: `seeds`).  With one of them set
 ONE grouped dip_adam_sgld_step_dev takes dip_adam_step_dev's place inside the bracket and the hipGraph, and the DipSgldState
@@ -154,7 +166,7 @@ class GroupedFits:
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
                  ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5,
-                 early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None):
+                 early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None, ssim=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
@@ -176,12 +188,16 @@ class GroupedFits:
         weight_decay / param_noise_std / param_noise_seeds: SGLD fits (dip_optim.FusedAdam(weight_decay=, noise_std=,
         noise_seed=) per instance): param_noise_std is one float or B floats -- a noise-level sweep in one launch list -- the
         seeds default to `seeds`.  With one of them set ONE grouped dip_adam_sgld_step_dev takes dip_adam_step_dev's place and
-        two rows join the slab behind everything else: the DipSgldState and the range table of the 4-D parameters."""
+        two rows join the slab behind everything else: the DipSgldState and the range table of the 4-D parameters.
+        ssim: None, or a utils.fit_monitor.GroupedSSIMMonitor: the mean structural similarity of every instance's output against
+        its ground truth (with_avg: of the GroupedFitMonitor's smoothed output too), inside the launch list behind the
+        early_stop= launches and in front of Adam; independent of the group kind.  Its rows join the slab behind the es_ rows."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
         self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks)
         self.early_stop = self._check_monitor_slot(early_stop, "early_stop")
+        self.ssim = self._check_ssim(ssim, B, self.monitor, exp_weight)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         self.weight_decay, self.param_noise_std, self.param_noise_seeds = self._check_sgld(
@@ -268,7 +284,7 @@ class GroupedFits:
             ex, mon = self._row0_extra, self.monitor
             own = (("saved", lambda b: net_inputs[b]), ("target", lambda b: targets[b]), ("mask", lambda b: self._mask4(masks[b])),
                    ("taps", lambda b: self.downsamplers[b]._taps), ("mon_gt", lambda b: mon.imgs_gt[b]),
-                   ("mon_hr", lambda b: mon.imgs_HR[b]))
+                   ("mon_hr", lambda b: mon.imgs_HR[b]), ("ssim_gt", lambda b: self.ssim.imgs_gt[b]))
             with torch.no_grad():
                 for b in range(B):
                     if b > 0:
@@ -301,20 +317,25 @@ class GroupedFits:
     def _devctx(self):
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
 
-    _SLOTS = (("monitor", "mon_", "_mdesc", "_mon"), ("early_stop", "es_", "_edesc", "_es"))
+    _SLOTS = (("monitor", "mon_", "_mdesc", "_mon"), ("early_stop", "es_", "_edesc", "_es"),
+              ("ssim", "ssim_", "_sdesc", "_ssim"))
 
     def _monitors(self):
-        """The monitors of this group in launch order -- monitor=, then early_stop=, both in front of Adam -- as (monitor, the
-        prefix of its slab rows' names, the attribute of its descriptor, the attribute of its launches)."""
+        """The monitors of this group in launch order -- monitor=, then early_stop=, then ssim=, all in front of Adam -- as
+        (monitor, the prefix of its slab rows' names, the attribute of its descriptor, the attribute of its launches)."""
         return [(getattr(self, slot), *rest) for slot, *rest in self._SLOTS if getattr(self, slot) is not None]
 
     @staticmethod
     def _check_monitor_slot(m, slot):
-        """What holds for monitor= and early_stop= alike: the types the slot takes, and that a monitor is adopted once."""
+        """What holds for monitor=, early_stop= and ssim= alike: the types the slot takes, and that a monitor is adopted once."""
         import utils.fit_monitor as FM
         if m is None:
             return None
-        if slot == "early_stop":
+        if slot == "ssim":
+            if not isinstance(m, FM.GroupedSSIMMonitor):
+                raise TypeError(f"dip-amd: GroupedFits(ssim=) takes a utils.fit_monitor.GroupedSSIMMonitor or None, got "
+                                f"{type(m).__name__} (a solo SSIMMonitor owns its buffers: they are no rows of the slab)")
+        elif slot == "early_stop":
             if not isinstance(m, FM.GroupedEarlyStopMonitor):
                 raise TypeError(f"dip-amd: GroupedFits(early_stop=) takes a utils.fit_monitor.GroupedEarlyStopMonitor or None, got "
                                 f"{type(m).__name__} (a solo EarlyStopMonitor owns its buffers: they are no rows of the slab)")
@@ -325,6 +346,24 @@ class GroupedFits:
         if m._adopted:
             raise RuntimeError(f"dip-amd: this {type(m).__name__} already belongs to a GroupedFits (a monitor is adopted once)")
         return m
+
+    @classmethod
+    def _check_ssim(cls, ssim, B, monitor, exp_weight):
+        """What can be said about `ssim` before anything is planned or allocated (the images' shape: _carve_monitor)."""
+        from utils.fit_monitor import GroupedFitMonitor
+        if ssim is None:
+            return None
+        cls._check_monitor_slot(ssim, "ssim")
+        if len(ssim.imgs_gt) != B:
+            raise ValueError(f"dip-amd: GroupedSSIMMonitor has {len(ssim.imgs_gt)} imgs_gt for {B} instances")
+        if ssim.with_avg and not isinstance(monitor, GroupedFitMonitor):
+            if exp_weight is not None:
+                raise NotImplementedError("dip-amd: GroupedSSIMMonitor(with_avg=True) with exp_weight= is not implemented (that "
+                                          "out_avg is no row of the slab and is updated behind Adam); use "
+                                          "monitor=GroupedFitMonitor(...), which carries the moving average")
+            raise ValueError("dip-amd: GroupedSSIMMonitor(with_avg=True) records the SSIM of the group's smoothed output: it "
+                             "needs monitor=GroupedFitMonitor(...), which keeps out_avg")
+        return ssim
 
     @classmethod
     def _check_monitor(cls, monitor, downsamplers, exp_weight, ema_init, targets, masks=None):
@@ -481,7 +520,7 @@ class GroupedFits:
         visit("sr_loss" if self.downsamplers is not None else "loss_head", "desc", self._head)
         pointer_args(self._head_fwd + self._head_bwd)
         for _, prefix, desc, ops in self._monitors():
-            visit("fit_monitor" if prefix == "mon_" else "early_stop", "desc", getattr(self, desc))
+            visit({"mon_": "fit_monitor", "es_": "early_stop"}.get(prefix, prefix[:-1]), "desc", getattr(self, desc))
             pointer_args(getattr(self, ops))
         for k, t in self._row0_extra.items():
             if t is not None:
@@ -602,9 +641,11 @@ class GroupedFits:
         eng, ex = self.eng, self._row0_extra
         if self.downsamplers is not None and prefix == "mon_":
             m._check_hr(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
+        if prefix == "ssim_":
+            m._check_out(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
         z = self._monitor_sizes(m)
         t = dict(out=ex["out"], out_LR=ex.get("y"), noisy=ex["target"], img=ex["target"], img_LR=ex["target"], mask=ex["mask"],
-                 mask_c=self.mask_c, hw=eng.Hout * eng.Wout, loss=ex["loss"])
+                 mask_c=self.mask_c, hw=eng.Hout * eng.Wout, loss=ex["loss"], avg=ex.get("mon_avg"))
         for b in m.BUFFERS:
             buf = None
             if b.when(m):
@@ -694,6 +735,7 @@ class GroupedFits:
             # (super-resolution: monitor.update(out_HR, out_LR, total_loss): the psnr_LR / psnr_HR record)
             # es.update(out): behind the monitor (a fall-back has been applied), in front of Adam -- best_params are the
             # parameters that produced best_out; every instance takes its own decision
+            # ssim.update(out): behind both (the monitor's out_avg is this iteration's)
             for _, _, _, ops in self._monitors():
                 for fn, args, name in getattr(self, ops):
                     N.check(fn(*args, st), name)

@@ -496,9 +496,19 @@ class NativeIteration:
         opt = FusedAdam(get_params('net', net, net_input), lr=LR, weight_decay=5e-8, noise_std=1e-4, noise_seed=0)
         pm = PosteriorMonitor(img_noisy, burn_in=7000, every=50)
         it = NativeIteration(net, head, opt, net_input, reg_noise=reg, posterior=pm)
-        it.run(num_iter); pm.mean, pm.variance(), pm.count"""
+        it.run(num_iter); pm.mean, pm.variance(), pm.count
 
-    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None, early_stop=None, posterior=None):
+    ssim=SSIMMonitor(img_gt, img_avg=None) is a fourth keyword: the mean structural similarity of the output against a ground
+    truth (utils.fit_monitor; with an SRHead img_gt is img_HR) as one more command array, dip_ssim_dev, behind the other three
+    and in front of Adam.  It stands behind monitor= so that with img_avg=monitor.out_avg the smoothed output it reads is this
+    iteration's.  It does not touch the fit; with ssim=None the plan's key is what it was.
+
+        sm = SSIMMonitor(img_gt, img_avg=monitor.out_avg, capacity=num_iter)
+        it = NativeIteration(net, head, opt, net_input, reg_noise=reg, monitor=monitor, ssim=sm)
+        it.run(num_iter); sm.history()                # [iters, 2]: ssim, ssim_sm"""
+
+    def __init__(self, net, head, optimizer, net_input, reg_noise=None, monitor=None, early_stop=None, posterior=None,
+                 ssim=None):
         import dip_group
         from utils.loss_head import MSEHead, SRHead
         from utils.reg_noise import RegNoise
@@ -521,7 +531,7 @@ class NativeIteration:
                              "opt_over with 'input' or 'down' goes through the eager closure")
         # (the monitor's type is refused before the first check that needs a GPU)
         self.monitor, self.device = monitor, getattr(net_input, "device", None)
-        self.early_stop, self.posterior = early_stop, posterior
+        self.early_stop, self.posterior, self.ssim = early_stop, posterior, ssim
         self._check_monitors()
         if not isinstance(net_input, torch.Tensor) or not net_input.is_cuda:
             raise RuntimeError("dip-amd: NativeIteration works on MI355X tensors only (net_input is on the CPU; no CPU "
@@ -563,9 +573,10 @@ class NativeIteration:
             raise NotImplementedError("dip-amd: eval-mode BatchNorm is not implemented (NativeIteration needs net.train())")
 
     def _monitors(self):
-        """The monitors of this iteration in launch order -- monitor=, then early_stop=, then posterior=, all in front of Adam
-        -- as (slot, monitor) pairs."""
-        return [(slot, getattr(self, slot)) for slot in ("monitor", "early_stop", "posterior") if getattr(self, slot) is not None]
+        """The monitors of this iteration in launch order -- monitor=, then early_stop=, then posterior=, then ssim=, all in
+        front of Adam -- as (slot, monitor) pairs."""
+        return [(slot, getattr(self, slot)) for slot in ("monitor", "early_stop", "posterior", "ssim")
+                if getattr(self, slot) is not None]
 
     def _check_monitors(self):
         """What can be said about monitor= and early_stop= before the output size is known (the image shape: _build)."""
@@ -575,7 +586,8 @@ class NativeIteration:
                  "early_stop": (FM.EarlyStopMonitor, "dip-amd: early_stop must be a utils.fit_monitor.EarlyStopMonitor or None",
                                 "keeps the parameters of"),
                  "posterior": (FM.PosteriorMonitor, "dip-amd: posterior must be a utils.fit_monitor.PosteriorMonitor or None",
-                               "samples")}
+                               "samples"),
+                 "ssim": (FM.SSIMMonitor, "dip-amd: ssim must be a utils.fit_monitor.SSIMMonitor or None", "records")}
         head = getattr(self, "head", None)
         for slot, m in self._monitors():
             types, refusal, copies = takes[slot]

@@ -19,6 +19,8 @@ the host reads the record table when it wants to print.
     PosteriorMonitor       no notebook has it either: the sample mean and variance of the outputs of an SGLD fit (Cheng et al.,
                            "A Bayesian Perspective on the Deep Image Prior"; dip_optim.FusedAdam(noise_std=)) after a burn-in,
                            dip_posterior_dev.  No record table: mean, variance(), count.  Solo only
+    SSIMMonitor            nor this: the mean structural similarity of the output against a ground truth (and of a smoothed
+                           output, img_avg=), dip_ssim_dev; columns ssim, ssim_sm.  ssim(x, y) is the one-shot function
 
 In the eager closure, after backward():
 
@@ -37,6 +39,7 @@ In the eager closure, after backward():
     mon = RestorationFitMonitor(net, img_var, mask_var, show_every=50, capacity=num_iter)
     es = EarlyStopMonitor(img_noisy_torch, window=100, patience=1000, net=net, capacity=num_iter)     # es.update(out)
     es = EarlyStopMonitor(img_noisy_torch, patience=1000, net=net, capacity=num_iter, mode='emv', alpha=0.1)
+    sm = SSIMMonitor(img_torch, img_avg=monitor.out_avg, capacity=num_iter)                           # sm.update(out)
 
 Inside the autograd-free iteration (no Python between the iterations) the same entry points read the iteration index from device
 memory (`monitor.counter`); `monitor.i` stays the host's count, and the two forms may alternate at any iteration boundary:
@@ -59,6 +62,7 @@ every instance takes its own decisions:
 
     mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)                           # GroupedFits(..., downsamplers=downs)
     mon = GroupedRestorationFitMonitor(show_every=50, capacity=num_iter)            # GroupedFits(..., masks=masks)
+    sm = GroupedSSIMMonitor(imgs_gt, capacity=num_iter)                             # GroupedFits(..., ssim=sm), any group kind
 
 A kind's device buffers are declared ONCE, in its table below (FIT_BUFFERS ...): the solo monitor allocates them, the group
 carves them from its slab and views them, and the plan's key and keep-alive list name them, all from that table.
@@ -126,6 +130,11 @@ POSTERIOR_BUFFERS = (Buf("mean", lambda z: z.n, lambda z: z.img, init="zero"),
                      Buf("m2", lambda z: z.n, lambda z: z.img, init="zero"),
                      Buf("samples", lambda z: 1, lambda z: z.one, _I32, "zero"),          # the descriptor's `count`
                      _COUNTER)
+_ssim_valid = lambda z: (*z.img[:-2], z.img[-2] - 10, z.img[-1] - 10)         # the valid positions of an 11 x 11 window
+SSIM_BUFFERS = (_image("gt", "gt", lambda m: True),
+                Buf("map", lambda z: int(np.prod(_ssim_valid(z))), _ssim_valid, when=lambda m: m.keep_map),
+                Buf("partial", lambda z: 2 * N.lib().dip_ssim_nblk(*z.img[-3:]), view=False),     # (out and avg: a row each)
+                _records(2), _COUNTER)
 
 
 # ---------------------------------------------------------------- descriptors and launches
@@ -172,9 +181,22 @@ def posterior_descriptor(m, t):
     return N.DipPosteriorDesc(p("out"), p("mean"), p("m2"), p("samples"), p("counter"), t["out"].numel(), m.burn_in, m.every)
 
 
+SSIM_WIN, SSIM_K1, SSIM_K2 = 11, 0.01, 0.03
+
+
+def ssim_descriptor(m, t):
+    """DipSsimDesc of monitor m (chw, data_range, with_avg, capacity): out, the optional second source `avg`, gt, the optional
+    map; c1 = (K1 data_range)^2, c2 = (K2 data_range)^2 and the pivot data_range / 2.  No `counter` in t: the functional form."""
+    p = lambda k: _ptr(t.get(k))
+    Cc, H, W = (int(s) for s in m.chw)
+    return N.DipSsimDesc(p("out"), p("avg") if m.with_avg else None, p("gt"), p("map"), p("partial"), p("records"), p("counter"),
+                         m.capacity, Cc, H, W, (SSIM_K1 * m.data_range) ** 2, (SSIM_K2 * m.data_range) ** 2,
+                         0.5 * m.data_range, N.lib().dip_ssim_nblk(Cc, H, W))
+
+
 _ENTRY = {N.DipFitMonitorDesc: "fit_monitor_dev", N.DipSRMonitorDesc: "sr_monitor_dev",
           N.DipRestoreMonitorDesc: "restore_monitor_dev", N.DipEarlyStopDesc: "early_stop_dev",
-          N.DipEarlyStopEmvDesc: "early_stop_emv_dev", N.DipPosteriorDesc: "posterior_dev"}
+          N.DipEarlyStopEmvDesc: "early_stop_emv_dev", N.DipPosteriorDesc: "posterior_dev", N.DipSsimDesc: "ssim_dev"}
 
 
 def monitor_launches(lib, desc, params_ptr=None, n_arena=0, arena_ptr=None):
@@ -238,6 +260,22 @@ def _early_stop_settings(who, mode, window, alpha, warmup, patience, capacity):
     return mode, int(window), float(alpha), int(warmup), int(patience), int(capacity)
 
 
+def _ssim_settings(who, img, data_range=1.0, capacity=1):
+    """(chw, data_range, capacity) of an SSIM over images shaped like `img`, or the error that says what is wrong: needs no GPU."""
+    if not isinstance(img, torch.Tensor):
+        raise TypeError(f"dip-amd: {who}: the images are tensors shaped like the net output ([1,C,H,W]), got {type(img).__name__}")
+    if img.dim() != 4 or img.shape[0] != 1 or img.shape[1] < 1:
+        raise ValueError(f"dip-amd: {who}: the images must be [1,C,H,W], got {tuple(img.shape)}")
+    if img.shape[2] < SSIM_WIN or img.shape[3] < SSIM_WIN:
+        raise ValueError(f"dip-amd: {who}: H and W must be >= {SSIM_WIN} (the {SSIM_WIN} x {SSIM_WIN} window is applied at valid "
+                         f"positions only), got {tuple(img.shape[2:])}")
+    if not 0.0 < float(data_range) < float("inf"):                  # (a NaN compares false)
+        raise ValueError(f"dip-amd: {who}: data_range must be positive and finite, got {data_range}")
+    if int(capacity) < 1:
+        raise ValueError(f"dip-amd: {who}: capacity must be > 0, got {capacity}")
+    return tuple(int(s) for s in img.shape[1:]), float(data_range), int(capacity)
+
+
 # ---------------------------------------------------------------- the kinds: what a solo and a grouped monitor share
 class _FitKind:
     COLUMNS = ("loss", "mse_noisy", "mse_gt", "mse_gt_sm", "psrn_noisy", "psrn_gt", "psrn_gt_sm", "fell_back")
@@ -276,6 +314,12 @@ class _PosteriorKind:
     COLUMNS = ()                                                    # no record table: mean, m2 and the sample count
     BUFFERS, ARENA, _descriptor = POSTERIOR_BUFFERS, None, posterior_descriptor
     head_kind = None
+
+
+class _SSIMKind:
+    COLUMNS = ("ssim", "ssim_sm")
+    BUFFERS, ARENA, _descriptor = SSIM_BUFFERS, None, ssim_descriptor
+    head_kind = None                                                # either head: the record needs the net output only
 
 
 class _Records:
@@ -767,6 +811,87 @@ class PosteriorMonitor(_PosteriorKind, _DeviceRecords):
         self._check_out(out.shape, "NativeIteration")
 
 
+class SSIMMonitor(_SSIMKind, _DeviceRecords):
+    """The mean structural similarity (SSIM; Wang, Bovik, Sheikh, Simoncelli 2004) of the net output against a ground truth on
+    the device, the number a restoration result is quoted with next to its PSNR: one record per iteration, {ssim, ssim_sm}.
+    Gaussian 11 x 11 window (sigma 1.5), K1 = 0.01, K2 = 0.03, biased covariances, valid positions only -- (H-10) x (W-10) per
+    channel -- and the mean over all channels and positions (dip_ssim_dev; include/dip_hip.h states the definition and the
+    arithmetic).  It aims at skimage.metrics.structural_similarity(gaussian_weights=True, use_sample_covariance=False,
+    data_range=data_range) and was not checked against that library.
+
+    `img_gt` is [1,C,H,W] like the net output.  img_avg= a second source of that shape, read where it lies (fp32, contiguous, on
+    the device): with img_avg=fit_monitor.out_avg -- call FitMonitor.update first -- `ssim_sm` is the SSIM of the denoising
+    notebook's smoothed result; without it the column is 0.  keep_map=True keeps S of the last iteration in `map`
+    ([1,C,H-10,W-10]).  update(out) is the eager form, after backward(); NativeIteration(ssim=this) issues the same entry point
+    behind monitor=, and the two may alternate.  It does not touch the fit."""
+    INPUTS, SETTINGS = ("avg",), ("chw", "data_range", "capacity")
+    _recorded = _DeviceRecords._advance            # update() goes through the device-indexed entry point: the counter moves
+
+    def __init__(self, img_gt, img_avg=None, data_range=1.0, keep_map=False, capacity=16384):
+        # (what needs no GPU is refused first: the types, the shapes, the settings)
+        self.chw, self.data_range, capacity = _ssim_settings("SSIMMonitor", img_gt, data_range, capacity)
+        if img_avg is not None:
+            if not isinstance(img_avg, torch.Tensor) or tuple(img_avg.shape) != tuple(img_gt.shape):
+                raise ValueError(f"dip-amd: SSIMMonitor: img_avg must be shaped like img_gt {tuple(img_gt.shape)}, got "
+                                 f"{tuple(getattr(img_avg, 'shape', ()))}")
+            if img_avg.dtype != torch.float32 or not img_avg.is_contiguous():
+                raise ValueError("dip-amd: SSIMMonitor: img_avg is read where it lies: it must be a contiguous fp32 tensor")
+        self.keep_map = bool(keep_map)
+        if not img_gt.is_cuda or (img_avg is not None and img_avg.device != img_gt.device):
+            raise RuntimeError("dip-amd: SSIMMonitor works on MI355X tensors only (no CPU fallback)")
+        self.gt = img_gt.detach().contiguous().float()
+        self.avg = None if img_avg is None else img_avg.detach()
+        self.shape, self.n = tuple(self.gt.shape), self.gt.numel()
+        self._init_device(img_gt.device, capacity, self.shape, n=self.n)
+
+    with_avg = property(lambda self: self.avg is not None)
+
+    def _check_out(self, shape, who):
+        if tuple(shape) != self.shape:
+            raise ValueError(f"dip-amd: {who}: the SSIMMonitor's img_gt is {self.shape}, the net output is {tuple(shape)}")
+
+    def update(self, out):
+        """Call once per closure evaluation, after backward() and behind FitMonitor.update (out_avg is then this iteration's)."""
+        self._update((out,))
+
+    def _check_update(self, o):
+        self._check_out(o.shape, "SSIMMonitor.update")
+        if not o.is_cuda or o.device != self.dev:
+            raise RuntimeError(f"dip-amd: SSIMMonitor.update: the output is on {o.device}, the monitor lives on {self.dev} "
+                               "(no CPU fallback)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dip-amd: SSIMMonitor.update cannot be captured into a hipGraph (the row index is "
+                               "host-synchronised state)")
+
+    def _issue(self, outs, lptr, stream):
+        self._sync_counter()
+        for fn, args, name in self._launches(self._dev_descriptor(outs[0])):
+            N.check(fn(*args, stream), name)
+
+    def _check_plan(self, out, head):
+        self._check_out(out.shape, "NativeIteration")
+
+
+def ssim(x, y, data_range=1.0, full=False):
+    """The SSIM of x against y ([1,C,H,W] on the device) as SSIMMonitor records it, through the same entry point: a 0-dim device
+    tensor (no host synchronisation), and with full=True also the map [1,C,H-10,W-10]."""
+    chw, data_range, _ = _ssim_settings("ssim", x, data_range)
+    if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(x.shape):
+        raise ValueError(f"dip-amd: ssim: x and y must have one shape, got {tuple(x.shape)} and {tuple(getattr(y, 'shape', ()))}")
+    if not x.is_cuda or y.device != x.device:
+        raise RuntimeError("dip-amd: ssim works on MI355X tensors only (no CPU fallback)")
+    x, y = x.detach().contiguous().float(), y.detach().contiguous().float()
+    m = SimpleNamespace(chw=chw, data_range=data_range, with_avg=False, capacity=1)
+    z = monitor_sizes(m, None, x.numel(), x.shape, (1,))
+    new = lambda name: torch.empty(next(b for b in SSIM_BUFFERS if b.name == name).count(z), dtype=_F32, device=x.device)
+    t = dict(out=x, gt=y, partial=new("partial"), records=new("records"), map=new("map") if full else None)
+    with torch.cuda.device(x.device):
+        for fn, args, name in monitor_launches(N.lib(), ssim_descriptor(m, t)):
+            N.check(fn(*args, torch.cuda.current_stream(x.device).cuda_stream), name)
+    value = t["records"][0]
+    return (value, t["map"].view(_ssim_valid(z))) if full else value
+
+
 # ---------------------------------------------------------------- B fits through one launch list
 class _GroupedRecords(_Records):
     """What the grouped monitors share: settings only, until a dip_group.GroupedFits adopts the monitor (once), carves the
@@ -924,3 +1049,28 @@ class GroupedEarlyStopMonitor(_EarlyStopKind, _GroupedRecords):
         with torch.no_grad():
             for r in rows:
                 params[r].copy_(self.best_params[r])
+
+
+class GroupedSSIMMonitor(_SSIMKind, _GroupedRecords):
+    """SSIMMonitor for the B fits of a dip_group.GroupedFits(..., ssim=this): settings only, until adopted.  A keyword of its own
+    next to monitor= and early_stop=, for all three group kinds (plain, masks=, downsamplers=: the record needs the net output
+    only; in a super-resolution group imgs_gt are the HR images).  The group that adopts it places, behind the es_ rows, the
+    ground truth, the partials, the records and the counter in its slab rows and exposes records [B, capacity, 2] and counter
+    [B] here.  ONE dip_ssim_dev call inside the group bracket, behind the monitor= and early_stop= launches and in front of
+    Adam, serves all B inside the ONE hipGraph of capture(); instance b's records are those of its solo fit, bit for bit.
+    with_avg=True records `ssim_sm` of the group's smoothed output too: it needs monitor=GroupedFitMonitor(...), whose out_avg
+    rows lie in the slab and are this iteration's when the call runs."""
+    keep_map = False                               # (no per-instance map: read g.out and call ssim(..., full=True))
+
+    def __init__(self, imgs_gt, with_avg=False, data_range=1.0, capacity=16384):
+        self.imgs_gt = list(imgs_gt) if imgs_gt is not None else []
+        if not self.imgs_gt or any(t is None for t in self.imgs_gt):
+            raise ValueError("dip-amd: GroupedSSIMMonitor: imgs_gt holds one ground truth per instance")
+        self.chw, self.data_range, capacity = _ssim_settings("GroupedSSIMMonitor", self.imgs_gt[0], data_range, capacity)
+        self._check_images(self.imgs_gt, [self.imgs_gt[0].shape] * len(self.imgs_gt), "imgs_gt", "imgs_gt[0]")
+        self.with_avg = bool(with_avg)
+        self._init_group(capacity)
+
+    def _check_out(self, B, out_shape):
+        """imgs_gt against the planned net output: one [1,C,H,W] image per instance."""
+        self._check_images(self.imgs_gt, [out_shape] * B, "imgs_gt", "the net output")

@@ -982,6 +982,54 @@ typedef struct DipPosteriorDesc {
 } DipPosteriorDesc;
 int dip_posterior_dev(const DipPosteriorDesc* d, void* stream);
 
+/* Mean structural similarity (SSIM; Wang, Bovik, Sheikh, Simoncelli 2004) of the network output -- and, optionally, of its
+ * moving average -- against a ground truth.  What it replaces is a host filter behind an `out.detach().cpu()` per iteration;
+ * the reference computes no SSIM.  Per channel of [C][H][W] images x (out, or avg) and y (gt):
+ *   window       Gaussian 11 x 11, separable, g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)) normalised to sum 1 in fp64, then rounded
+ *                to fp32;
+ *   moments      mu_x, mu_y, E[xx], E[yy], E[xy] by that filter over VALID positions only, (H - 10) x (W - 10) per channel
+ *                (no padding: what cropping a 5-pixel border after filtering amounts to);
+ *   covariances  biased: s_xx = E[xx] - mu_x^2, s_yy, s_xy alike;
+ *   map          S = ((2 mu_x mu_y + c1)(2 s_xy + c2)) / ((mu_x^2 + mu_y^2 + c1)(s_xx + s_yy + c2)), with
+ *                c1 = (0.01 data_range)^2 and c2 = (0.03 data_range)^2 from the caller;
+ *   ssim         the mean of S over all channels and valid positions.
+ * Arithmetic (fp32): the moments are formed about `pivot` (data_range / 2): a = x - pivot, b = y - pivot and the products
+ * a a, b b, a b, each rounded once, go through the horizontal and then the vertical 11-tap chain h <- fma(g[k], v[k], h) in tap
+ * order from zero; s_xx = E[aa] - mu_a mu_a (variances do not see the shift, and most of the cancellation of E[xx] - mu_x^2
+ * is gone), mu_x = mu_a + pivot.  The four factors are formed from individually rounded operations, never contracted:
+ *   n1 = 2 (mu_x mu_y) + c1;  n2 = 2 s_xy + c2;  d1 = (mu_x mu_x + mu_y mu_y) + c1;  d2 = (s_xx + s_yy) + c2;
+ *   S = (n1 n2) / (d1 d2), a correctly rounded division.
+ * With x == y bit for bit, n1 == d1 and n2 == d2 bit for bit: every S is exactly 1.0f, and so is the mean.
+ * One workgroup owns a tile of 16 x 64 valid outputs of one channel and leaves ONE fp32 partial: every thread adds its four S
+ * in row order, then a 256-wide LDS tree in a fixed pairing order (invalid positions contribute 0).  A one-block kernel adds
+ * the dip_ssim_nblk(C, H, W) partials of a source in fp64 in a fixed order (64 lanes, lane t the partials t, t + 64, ...,
+ * then the lane sums in lane order), divides by C (H-10) (W-10) and rounds once to fp32.  Deterministic: no float atomics, no
+ * last-block ticket, nothing synchronises.
+ *   record <- {ssim, ssim_sm}    (2 floats per row; ssim_sm is the SSIM of `avg` against gt, 0 when avg is NULL)
+ * counter != NULL: the iteration index i = counter[0] lives in DEVICE memory, the row is records + 2*i and the last store is
+ * counter[0] <- i + 1; i outside [0, capacity) writes nothing at all -- map, partial, records and counter are left alone
+ * (callers check the capacity first).  counter == NULL is the functional form: row 0, nothing advanced, capacity not read.
+ * `map` (NULL: not stored) receives S of `out`, [C][H-10][W-10].  `partial` is scratch of nblk floats, 2*nblk with avg.
+ * out, gt, partial and records are required; C >= 1, H >= 11, W >= 11, nblk == dip_ssim_nblk(C, H, W) (which is -1 for
+ * sizes it refuses), capacity > 0 with a counter; otherwise -1 before anything is launched.  sizeof(DipSsimDesc) == 88 (LP64).
+ * Grouped instantiations: family DIP_FAM_LOSS (every non-NULL pointer in instance 0's slab, instance b works on the same
+ * fields advanced by b * stride). */
+typedef struct DipSsimDesc {
+    const float* out;       /* [C][H][W] the network output of this iteration */
+    const float* avg;       /* [C][H][W] a second source (the smoothed output) or NULL */
+    const float* gt;        /* [C][H][W] the ground truth */
+    float* map;             /* [C][H-10][W-10] S of `out`, or NULL */
+    float* partial;         /* nblk floats of scratch (2*nblk with avg) */
+    float* records;         /* [capacity][2] */
+    int* counter;           /* int32[1]: the iteration index, advanced by the call; NULL: row 0, nothing advanced */
+    int capacity;
+    int C, H, W;
+    float c1, c2, pivot;
+    int nblk;               /* dip_ssim_nblk(C, H, W) */
+} DipSsimDesc;
+int dip_ssim_nblk(int C, int H, int W);
+int dip_ssim_dev(const DipSsimDesc* d, void* stream);
+
 /* ---------------------------------------------------------------- Lanczos down-sampler ---- */
 /* Downsampler.forward (models/downsampler.py:65-71): ReplicationPad2d(pad) + depth-wise
  * k x k stride-`factor` correlation with the fixed taps; NCHW [C][H][W] -> [C][H/f][W/f]. */
