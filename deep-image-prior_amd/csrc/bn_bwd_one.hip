@@ -16,7 +16,7 @@
 // channels against 12.1 / 12.5 us for the three launches -- and 34 / 135 us at 64^2 / 128^2 against 13 / 19: a workgroup
 // that owns 4 of 128 channels uses 16 bytes of every 128-byte line it pulls into its L1, so 32 CUs deliver 1/8 of their
 // fill bandwidth, and owning 32 channels (whole lines) leaves 4 CUs: ownership needs few CUs, bandwidth needs many.  The
-// form therefore serves <= 1024 pixels only (DIP_BNB_ONE_MAX_PIXELS); in the iteration it removes 12 launches of the
+// form therefore serves <= 1024 pixels only (ONE_MAX_PIXELS); in the iteration it removes 12 launches of the
 // default net (244 -> 232) and 9 of the 'library' net for +-0 / +0.4 % it/s: what the low-resolution walk waits for is
 // dependent memory round trips, not launches (DESIGN.md section 3.7 said so; this is the measurement).
 // Deterministic (fixed pixel -> thread map, fixed reduction order); the rounded product dz = du * act'(z) is the same
@@ -24,7 +24,6 @@
 #include "dip_common.h"
 #include "dip_group.h"
 #include "dip_gradsrc.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -138,20 +137,14 @@ __global__ __launch_bounds__(ONE_NT) void bn_bwd_one_kernel(const DipGradSrc src
     if (p < npix) apply(p, du_of(p), ld4(y + (size_t)p * Cy + ch));
 }
 
-int one_max_pixels() {
-    static const int v = [] {
-        const char* e = getenv("DIP_BNB_ONE_MAX_PIXELS");
-        return e ? atoi(e) : 1024;
-    }();
-    return v;
-}
+constexpr int ONE_MAX_PIXELS = 1024;      // 32 x 32: above that a 4-channel slice of the plane costs 8x its bytes in L1 fills
 
 }  // namespace
 
-// 1 when the engine should run a BatchNorm backward over npix pixels x C channels as ONE launch (DIP_BNB_ONE_MAX_PIXELS,
-// default 1024; 0 switches the form off)
+// 1 when the engine should run a BatchNorm backward over npix pixels x C channels as ONE launch (<= ONE_MAX_PIXELS;
+// DIP_BNB_NO_ONE=1 makes the engine skip the form)
 extern "C" int dip_bn_bwd_one_ok(int npix, int C) {
-    return (npix >= 1 && npix <= one_max_pixels() && C >= 1 && C <= 4096) ? 1 : 0;
+    return (npix >= 1 && npix <= ONE_MAX_PIXELS && C >= 1 && C <= 4096) ? 1 : 0;
 }
 
 extern "C" int dip_bn_bwd_one(const DipGradSrc* src, const float* y, int H, int W, int Cy, int C, const float* state, int Cs,

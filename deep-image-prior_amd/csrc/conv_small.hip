@@ -21,7 +21,7 @@
 //     wave only visits the taps that hit non-zero positions of the dilated gradient (9 taps per 4
 //     pixels instead of 36, as the phase mode of the LDS-DMA kernel).
 // Any stride-1/2 1x1 / 3x3 convolution or data gradient with reflection / zero / replication padding,
-// any activation, 1..160 output channels; the engine uses it below DIP_SMALL_MAX_PIXELS output pixels.
+// any activation, 1..160 output channels; the engine uses it up to SMALL_MAX_PIXELS output pixels.
 #include "dip_common.h"
 #include "dip_group.h"
 #include <stdlib.h>
@@ -62,18 +62,6 @@ __device__ __forceinline__ void sm_ring_pixel(int i, int H, int W, int& r, int& 
 // K steps (8 input channels of one tap = 4 MFMAs) a wave keeps in flight at once; 16 waves x 64 lanes x (8 * SMAX + ..)
 // registers must fit the 512-register file of a SIMD four times
 template <int NW> struct SmCfg { static constexpr int SMAX = NW == 16 ? 10 : 18; };
-
-__device__ __forceinline__ int sm_map_src(int v, int n_in, int dil, int pad_mode) {
-    const int nv = (n_in - 1) * dil + 1;
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, nv);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), nv - 1);
-    if (v < 0 || v >= nv) return -1;
-    if (dil == 2) {
-        if (v & 1) return -1;
-        v >>= 1;
-    }
-    return v;
-}
 
 // "the two loads of this K step have landed" (N younger loads may still be in flight); the registers are in/out operands
 // so that no use of them can be scheduled above the wait
@@ -151,8 +139,8 @@ __global__ __launch_bounds__(64 * NW) void conv_small_kernel(const DipConvDesc d
         const int oy = iy * pstep + py, ox = ix * pstep + px;
         if (t < KK) {
             const int ky = t / d.ks, kx = t - ky * d.ks;
-            const int sr = sm_map_src(oy * d.stride + ky - d.off, d.Hin, d.dil, d.pad_mode);
-            const int sc = sm_map_src(ox * d.stride + kx - d.off, d.Win, d.dil, d.pad_mode);
+            const int sr = dip_map_src_dil(oy * d.stride + ky - d.off, d.Hin, d.dil, d.pad_mode);
+            const int sc = dip_map_src_dil(ox * d.stride + kx - d.off, d.Win, d.dil, d.pad_mode);
             srcoff[t][p] = (pvalid && sr >= 0 && sc >= 0) ? sr * d.Win + sc : -1;
         } else {
             const int pitch = d.y_pitch > 0 ? d.y_pitch : d.Wout;
@@ -342,13 +330,7 @@ __global__ __launch_bounds__(64 * NW) void conv_small_kernel(const DipConvDesc d
     }
 }
 
-int small_max_pixels() {
-    static const int v = [] {
-        const char* e = getenv("DIP_SMALL_MAX_PIXELS");
-        return e ? atoi(e) : 4624;             // 68 x 68: the 64 x 64 layers and their padded-domain data gradients
-    }();
-    return v;
-}
+constexpr int SMALL_MAX_PIXELS = 4624;         // 68 x 68: the 64 x 64 layers and their padded-domain data gradients
 
 bool small_geom(const DipConvDesc& d, SmallGeom* g) {
     if (d.ks != 1 && d.ks != 3 && d.ks != 5 && d.ks != 7) return false;
@@ -384,8 +366,6 @@ bool small_geom(const DipConvDesc& d, SmallGeom* g) {
     const int tmax = kcls * kcls * ((d.Cin + 7) / 8);
     int nw = 4;
     while (nw < 16 && tmax > nw * SmCfg<8>::SMAX / 2) nw *= 2;
-    static const char* force = getenv("DIP_SMALL_NW");
-    if (force && (atoi(force) == 4 || atoi(force) == 8 || atoi(force) == 16)) nw = atoi(force);
     g->nw = nw;
     return true;
 }
@@ -426,7 +406,7 @@ int small_launch_nw(const DipConvDesc& d, const SmallGeom& g, hipStream_t st) {
 extern "C" int dip_conv_dgrad_ring_ok(const DipConvDesc* dp) {
     const DipConvDesc& d = *dp;
     static const bool off = getenv("DIP_CONV_NO_RING") != nullptr;
-    static const int maxpix = getenv("DIP_DGRAD_RING_MAX") ? atoi(getenv("DIP_DGRAD_RING_MAX")) : 300000;
+    constexpr int maxpix = 300000;         // up to 512 x 512
     SmallGeom g;
     if (off || !small_geom(d, &g)) return 0;
     if (d.ks != 3 || d.stride != 1 || d.dil != 1 || d.off != 1 || d.pad_mode != DIP_PAD_ZERO) return 0;
@@ -461,18 +441,17 @@ extern "C" int dip_conv_dgrad_ring(const DipConvDesc* dp, void* stream) {
 //     tile per CU doing 10 us of MFMAs on <= 40 CUs, and the tiled kernel's 24-way split-K + finish is 4 us faster.
 extern "C" int dip_conv_small_eligible(const DipConvDesc* dp) {
     static const bool off = getenv("DIP_CONV_NO_SMALL") != nullptr;
-    static const int k5_d2 = getenv("DIP_SMALL_K5_DIL2_MAX_PIXELS") ? atoi(getenv("DIP_SMALL_K5_DIL2_MAX_PIXELS")) : 24000;
-    static const int k5_s2 = getenv("DIP_SMALL_K5_S2_MAX_PIXELS") ? atoi(getenv("DIP_SMALL_K5_S2_MAX_PIXELS")) : 5000;
-    static const int k5_min = getenv("DIP_SMALL_K5_MIN_PIXELS") ? atoi(getenv("DIP_SMALL_K5_MIN_PIXELS")) : 600;
+    constexpr int k5_d2 = 24000, k5_s2 = 5000, k5_min = 600;      // (all three from the sweep above)
+    static_assert(k5_d2 >= SMALL_MAX_PIXELS && k5_s2 >= SMALL_MAX_PIXELS, "the 5x5 bounds widen the 3x3 bound");
     SmallGeom g;
     if (off || !small_geom(*dp, &g)) return 0;
     const int px = dp->Hout * dp->Wout;
     if (dp->ks >= 5) {
-        if (dp->dil == 2) return px <= (k5_d2 > small_max_pixels() ? k5_d2 : small_max_pixels()) ? 1 : 0;
-        if (dp->stride == 2) return px <= (k5_s2 > small_max_pixels() ? k5_s2 : small_max_pixels()) ? 1 : 0;
+        if (dp->dil == 2) return px <= k5_d2 ? 1 : 0;
+        if (dp->stride == 2) return px <= k5_s2 ? 1 : 0;
         if (dp->ks * dp->ks * dp->Cin >= 3200 && px < k5_min) return 0;
     }
-    return px <= small_max_pixels() ? 1 : 0;
+    return px <= SMALL_MAX_PIXELS ? 1 : 0;
 }
 
 // rows of the partial buffers (stats: [rows][3][CoutP32]; bnb_partials: [rows][2][bnb_Cs]) of dip_conv_small(d)

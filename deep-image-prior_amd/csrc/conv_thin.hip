@@ -26,12 +26,6 @@ namespace {
 
 typedef float f32x4t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int tmap_src(int v, int n_in, int pad_mode) {
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
-    return (v < 0 || v >= n_in) ? -1 : v;
-}
-
 template <int KS, int S>
 struct TCfg {
     static constexpr int TH = 8, TW = 16;
@@ -43,7 +37,7 @@ struct TCfg {
 // NCB: 16-column blocks of the output (1 .. 4).  cc: input channels per chunk (16, 32 or 64).
 template <int KS, int S, int NCB, bool GRP = false>
 __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, const int ntx, const int ntiles, const int cc,
-                                                        const int rpg, const int CoutP32, const int knock, const DipGrpArg<GRP> grp) {
+                                                        const int rpg, const int CoutP32, const DipGrpArg<GRP> grp) {
     DIP_GRP_DESC(DipConvDesc, d);
     using C = TCfg<KS, S>;
     constexpr int CP16 = NCB * 16;
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, co
             const int nslots = C::NPIX * cc4;
             // batches of 8 slots per thread: all eight loads are issued (clamped addresses, no control flow around them)
             // before the first one is used -- one memory round trip per batch instead of one per slot
-            for (int f0 = tid; f0 < nslots && !(knock & 2); f0 += 256 * 8) {       // (knock: timing-only switches, DIP_THIN_KNOCK)
+            for (int f0 = tid; f0 < nslots; f0 += 256 * 8) {
                 f32x4t v[8];
                 bool ok[8];
 #pragma unroll
@@ -95,8 +89,8 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, co
                     const int f = f0 + i * 256;
                     const int hp = (f < nslots ? f : tid) >> csh;
                     const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-                    const int sr = tmap_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
-                    const int sc = tmap_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
+                    const int sr = dip_map_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
+                    const int sc = dip_map_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
                     ok[i] = sr >= 0 && sc >= 0 && cvalid;
                     v[i] = *reinterpret_cast<const f32x4t*>(d.x + (ok[i] ? ((size_t)sr * d.Win + sc) * d.Cx + c : 0));
                 }
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, co
             // ---- the group's weights of the chunk: [tap][c / 4][o][c % 4], CP16 columns of the CoutP32 packed ones -----
             {
                 const int nslots = ntap * cc4 * CP16;
-                for (int g0 = tid; g0 < nslots && !(knock & 4); g0 += 256 * 8) {          // batches of 8 loads in flight, as for the halo
+                for (int g0 = tid; g0 < nslots; g0 += 256 * 8) {          // batches of 8 loads in flight, as for the halo
                     f32x4t w[8];
                     bool ok[8];
 #pragma unroll
@@ -163,7 +157,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, co
             };
             readA(tap0, 0);
             readB(0, 0);
-            const int nsteps = (knock & 1) ? 0 : ntap * nj;
+            const int nsteps = ntap * nj;
             int tl = 0, j = 0;
             for (int s = 0; s < nsteps; ++s) {
                 const f32x4t ca0 = a0, ca1 = a1;
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const DipConvDesc d_, co
         mean[cb] = cn > 0.f ? k0 + s1 / cn : 0.f;
         M2[cb] = cn > 0.f ? s2 - s1 * s1 / cn : 0.f;
     }
-    if (d.stats == nullptr || (knock & 8)) return;
+    if (d.stats == nullptr) return;
     // the four lanes (q) of a column, then the four waves, combined in a fixed order (Chan et al.)
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
@@ -250,7 +244,7 @@ template <int KS, int S>
 int thin_cc(int Cin, int ncb, int* rpg_out, int* lds_bytes) {
     using C = TCfg<KS, S>;
     const int cin16 = dip_round_up(Cin, 16);
-    static const int budget = getenv("DIP_THIN_LDS_KB") ? atoi(getenv("DIP_THIN_LDS_KB")) * 1024 : 64 * 1024;
+    constexpr int budget = 64 * 1024;
     int best = 0, best_work = 0, fb = 0, fb_bytes = 1 << 30, fb_rpg = 0;
     for (int cc = 16; cc <= 64 && cc <= cin16; cc *= 2)
         for (int rpg = 1; rpg <= KS; ++rpg) {
@@ -268,10 +262,7 @@ bool thin_off() {
     static const bool off = getenv("DIP_CONV_NO_THIN") != nullptr;
     return off;
 }
-int thin_min_pixels() {
-    static const int v = getenv("DIP_THIN_MIN_PIXELS") ? atoi(getenv("DIP_THIN_MIN_PIXELS")) : 4625;      // below: conv_small
-    return v;
-}
+constexpr int THIN_MIN_PIXELS = 4625;      // below: conv_small
 
 // shape part of the eligibility (what dip_conv_plan can know)
 bool thin_shape_ok(int Hout, int Wout, int Cin, int Cout, int ks, int stride) {
@@ -279,7 +270,7 @@ bool thin_shape_ok(int Hout, int Wout, int Cin, int Cout, int ks, int stride) {
     if (ks != 3 && ks != 5) return false;
     if (stride != 1 && stride != 2) return false;
     if (Cin < 1 || Cin > 64 || Cout < 1 || Cout > 64) return false;
-    if (Hout * Wout < thin_min_pixels()) return false;
+    if (Hout * Wout < THIN_MIN_PIXELS) return false;
     // MEASURED (tools/thin_sweep.py on the 'library' net's shapes, profiles/r06_thin_sweep_conv_thin.txt; us, this kernel
     // against the register-staged / LDS-DMA kernels it replaces): it wins where ONE chunk holds all channels and all taps'
     // weights (<= 51 KB) --  16>16 5x5 @224x352 21.6 / 36.3 (data gradient 20.2 / 33.4), 16>32 5x5 s2 24.8 / 32.6, 32>16 3x3
@@ -307,9 +298,8 @@ int thin_launch(const DipConvDesc& d, hipStream_t st) {
         if (e != hipSuccess) { dip_set_error(hipGetErrorString(e)); return (int)e; }
     }
     const int ntx = dip_cdiv(d.Wout, C::TW), nty = dip_cdiv(d.Hout, C::TH);
-    static const int knock = getenv("DIP_THIN_KNOCK") ? atoi(getenv("DIP_THIN_KNOCK")) : 0;      // timing-only knock-outs (wrong results)
     dip_launch_pair<DIP_FAM_CONV>(kern, kern_g, dim3(ntx * nty), dim3(256), (size_t)lds, st, d, ntx, ntx * nty, cc, rpg,
-                                  dip_round_up(d.Cout, 32), knock);
+                                  dip_round_up(d.Cout, 32));
     DIP_CHECK_LAUNCH();
     return 0;
 }

@@ -24,6 +24,7 @@ constexpr int T4_TH = 16, T4_TW = 16, T4_HH = T4_TH + 2, T4_HW = T4_TW + 2, T4_N
 constexpr int T4_PITCH = 36;                                   // dwords per halo pixel (32 channels + 4 pad)
 constexpr int T4_SLOTS = (T4_NPIX * 8 + 255) / 256;            // 16-byte pieces per thread and chunk
 
+// (own form, not dip_map_src: takes a flag -- every padding mode other than DIP_PAD_ZERO reflects -- one compare less)
 __device__ __forceinline__ int t4_map_src(int v, int n_in, int reflect) {
     if (reflect) v = dip_reflect(v, n_in);
     return (v < 0 || v >= n_in) ? -1 : v;
@@ -307,10 +308,8 @@ __global__ __launch_bounds__(256) void conv_thin4_mfma_kernel(const DipConvDesc 
 }
 
 // Rows per walk.  A walk costs (TH + 2) rows of 96 MFMAs and the chip has 1024 SIMDs: with k walks per SIMD the launch lasts
-// k (TH_k + 2) rows, TH_k = the smallest height whose walks number <= 1024 k.  k = 1 .. 4 are compared (DIP_THIN4_TH overrides).
+// k (TH_k + 2) rows, TH_k = the smallest height whose walks number <= 1024 k.  k = 1 .. 4 are compared.
 int t4m_th(int Hout, int Wout) {
-    static const int forced = getenv("DIP_THIN4_TH") ? atoi(getenv("DIP_THIN4_TH")) : 0;
-    if (forced > 0) return forced;
     const int strips = dip_cdiv(Wout, T4M_SW);
     int best = 0, best_cost = 1 << 30;
     for (int k = 1; k <= 4; ++k) {

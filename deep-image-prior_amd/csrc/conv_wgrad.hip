@@ -34,12 +34,6 @@ struct WCfg {
     static constexpr int NGROUPS = (KS * KS + NT - 1) / NT;
 };
 
-__device__ __forceinline__ int wmap_src(int v, int n_in, int pad_mode) {
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
-    return (v < 0 || v >= n_in) ? -1 : v;
-}
-
 template <int KS, int S, int NT, int CB, bool SLIDE = false, bool GRP = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const DipWgradDesc d_, const int ntx, const int ntiles,
                                                             const int CinP, const int CoutP, const int ragged_parts,
@@ -121,8 +115,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const DipWgradDesc d
             if (f < C::NPIX * (C::CW / 4)) {
                 const int hp = f / (C::CW / 4);
                 const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-                const int sr = wmap_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
-                const int sc = wmap_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
+                const int sr = dip_map_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
+                const int sc = dip_map_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
                 if (sr >= 0 && sc >= 0 && cvalid)
                     v = *reinterpret_cast<const f32x4*>(d.x + ((size_t)sr * d.Win + sc) * d.Cx + c0 + c4 * 4);
                 else
@@ -188,8 +182,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const DipWgradDesc d
             if (f < C::NPIX * (C::CW / 4)) {
                 const int hp = f / (C::CW / 4);
                 const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-                const int sr = wmap_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
-                const int sc = wmap_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
+                const int sr = dip_map_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
+                const int sc = dip_map_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
                 f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (sr >= 0 && sc >= 0 && cvalid) {
                     v = *reinterpret_cast<const f32x4*>(d.x + ((size_t)sr * d.Win + sc) * d.Cx + c0 + c4 * 4);
@@ -809,15 +803,6 @@ extern "C" int dip_wgrad_plan(int Hout, int Wout, int Cin, int Cout, int ks, int
     const int min_tiles = (ks == 3 && stride == 2) ? 2 : 4;
     if (n > nt / min_tiles) n = nt / min_tiles;
     if (n < 1) n = 1;
-    // the layers wgrad_bf3_kernel takes (3x3 stride 1, >= 512 tiles of 2 x 16 pixels): ONE 8-wave workgroup per CU that fills its
-    // register file, resident for the whole launch -- 256 of them leave no CU to the dependent chain of the main stream, which then
-    // waits for the launch to end (profiles/r06_timeline_three_streams.txt: a 6 us bn_bwd_finalize "runs" 450 us beside the 512^2
-    // weight gradient).  DIP_WGRAD_BF3_WGS caps the grid so that 256 - cap CUs stay free for the chain.
-    static const int bf3_wgs = [] { const char* e = getenv("DIP_WGRAD_BF3_WGS"); return e ? atoi(e) : 0; }();
-    if (bf3_wgs > 0 && ks == 3 && stride == 1 && Cin >= 32 && Cout >= 97 && dip_cdiv(Wout, 16) * dip_cdiv(Hout, 2) >= 512) {
-        const int cap = bf3_wgs / (dip_cdiv(chunks, 2) * dip_cdiv(CoutP, 128));
-        if (cap >= 1 && n > cap) n = cap;
-    }
     const long long slab = (long long)ks * ks * CinP * CoutP;
     while (n > 1 && (long long)n * slab > (64ll << 20)) n /= 2;
     *nsplit = n * wgrad_kw(CoutP);         // narrow layers: kw slabs per workgroup

@@ -152,6 +152,25 @@ __device__ __forceinline__ int dip_xcd_remap(int bid, int nwg) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Thread layout shared by the NHWC streaming kernels (bn_kernels.hip, upcat_kernels.hip): a block of 256 threads walks a
+// pixel range; thread (prow, cg) handles 4 channels [4cg, 4cg+4) of pixels prow, prow+RPI, ...   (RPI = 256 / NC4)
+// ---------------------------------------------------------------------------------------------
+struct RowLayout {
+    int nc4, rpi, prow, cg;
+    bool active;
+};
+__device__ __forceinline__ RowLayout row_layout(int C) {
+    RowLayout L;
+    L.nc4 = (C + 3) >> 2;
+    L.rpi = 256 / L.nc4;
+    if (L.rpi < 1) L.rpi = 1;
+    L.prow = threadIdx.x / L.nc4;
+    L.cg = threadIdx.x - L.prow * L.nc4;
+    L.active = (int)threadIdx.x < L.rpi * L.nc4;
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Block-level tree reductions for the NHWC streaming kernels.  Thread (prow, cg) owns 4 channels;
 // the `rpi` threads that share a channel group `cg` are combined in log2(rpi) steps through LDS
 // (a single thread looping over 255 partners was measured at 80-90 us for thin, 4-channel tensors).

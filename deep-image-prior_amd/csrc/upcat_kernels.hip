@@ -20,21 +20,6 @@ __device__ __forceinline__ void bil_src(int dst, int n_in, int& i0, int& i1, flo
     l0 = 1.f - l1;
 }
 
-struct RowLayout {
-    int nc4, rpi, prow, cg;
-    bool active;
-};
-__device__ __forceinline__ RowLayout row_layout(int C) {
-    RowLayout L;
-    L.nc4 = (C + 3) >> 2;
-    L.rpi = 256 / L.nc4;
-    if (L.rpi < 1) L.rpi = 1;
-    L.prow = threadIdx.x / L.nc4;
-    L.cg = threadIdx.x - L.prow * L.nc4;
-    L.active = (int)threadIdx.x < L.rpi * L.nc4;
-    return L;
-}
-
 // partial row of this block -> d.stats; with fin.state != NULL the last block to arrive finalises the BatchNorm (bn_ticket.h)
 __device__ __forceinline__ void upcat_rows_out(const DipUpcatDesc& d, const DipBnFin& fin, const RowLayout& L, float n,
                                                const f32x4& mean, const f32x4& M2, int C, double* shd, unsigned* flag) {

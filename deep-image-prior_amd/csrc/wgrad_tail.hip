@@ -23,7 +23,6 @@
 //     phase 2 of the fp32 kernel, which shared the tail out among <= 8 workgroups per walker): no LDS, no barrier.
 #include "dip_common.h"
 #include "dip_group.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -38,7 +37,8 @@ template <> struct WtVec<4> { typedef f32x4 T; };
 template <int NCB> __device__ __forceinline__ float wt_get(const typename WtVec<NCB>::T& v, int e) { return v[e]; }
 template <> __device__ __forceinline__ float wt_get<1>(const float& v, int) { return v; }
 
-// source index of v under the padding rule, -1 outside (zero padding); selects, not a wave-uniform switch per call
+// source index of v under the padding rule, -1 outside (zero padding); selects, not a wave-uniform switch per call (own
+// form on purpose: dip_map_src branches on pad_mode)
 __device__ __forceinline__ int wt_map(int v, int n, int pad_mode) {
     const int a = v < 0 ? -v : v;
     const int refl = a >= n ? 2 * (n - 1) - a : a;
@@ -217,12 +217,11 @@ int wt_launch(const DipWgradDesc& d, hipStream_t st, int c_base) {
 }  // namespace
 
 // 1 when dip_wgrad_tail_stream serves the tail of `d`: 3x3, stride 1, 1..4 channels behind >= 1 whole 32-channel chunk
-// (DIP_WGRAD_TAIL_OLD=1: phase 2 of the fp32 kernel as before, for A/B runs)
+// (the other shapes keep phase 2 of the fp32 kernel)
 extern "C" int dip_wgrad_tail_stream_ok(const DipWgradDesc* dp) {
     const DipWgradDesc& d = *dp;
-    static const bool off = getenv("DIP_WGRAD_TAIL_OLD") != nullptr;
     const int tail = d.Cin & 31;
-    return (!off && d.ks == 3 && d.stride == 1 && tail >= 1 && tail <= 4 && d.Cin > 32 && d.nsplit >= 1 && !(d.Cx & 3) && !(d.Cdy & 3) &&
+    return (d.ks == 3 && d.stride == 1 && tail >= 1 && tail <= 4 && d.Cin > 32 && d.nsplit >= 1 && !(d.Cx & 3) && !(d.Cdy & 3) &&
             (long long)d.Hin * d.Win * d.Cx < (1ll << 31) && (long long)d.Hout * d.Wout * d.Cdy < (1ll << 31)) ? 1 : 0;
 }
 
@@ -231,11 +230,9 @@ extern "C" int dip_wgrad_tail_stream(const DipWgradDesc* dp, void* stream) {
     if (!dip_wgrad_tail_stream_ok(dp)) DIP_FAIL("wgrad_tail_stream: needs a 3x3 stride-1 layer with a 1..4-channel tail behind whole 32-channel chunks");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int c_base = (d.Cin >> 5) << 5;
-    // columns per workgroup: as many as still give >= 256 workgroups (DIP_WGRAD_TAIL_NCB overrides)
-    static const int forced = [] { const char* e = getenv("DIP_WGRAD_TAIL_NCB"); return e ? atoi(e) : 0; }();
+    // columns per workgroup: as many as still give >= 256 workgroups
     const int CoutP = dip_round_up(d.Cout, 32);
     int ncb = 2;                                     // (4 columns per lane: the pipelined loads do not fit the register file)
     while (ncb > 1 && d.nsplit * dip_cdiv(CoutP, 32 * ncb) < 256) ncb >>= 1;
-    if (forced == 1 || forced == 2) ncb = forced;
     return ncb == 2 ? wt_launch<2>(d, st, c_base) : wt_launch<1>(d, st, c_base);
 }

@@ -21,12 +21,6 @@ namespace {
 
 typedef float f32x4w __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ int wt_map_src(int v, int n_in, int pad_mode) {
-    if (pad_mode == DIP_PAD_REFLECT) v = dip_reflect(v, n_in);
-    else if (pad_mode == DIP_PAD_REPLICATE) v = min(max(v, 0), n_in - 1);
-    return (v < 0 || v >= n_in) ? -1 : v;
-}
-
 template <int KS, int S, int CI, int CO>
 struct WTCfg {
     static constexpr int TH = 8, TW = 16;
@@ -106,8 +100,8 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(const DipWgradDesc d_, 
             const int f = tid + i * 256;
             const int hp = min(f, C::NPIX * 4 * CI - 1) / (4 * CI);
             const int hr = hp / C::HTW, hc = hp - hr * C::HTW;
-            const int sr = wt_map_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
-            const int sc = wt_map_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
+            const int sr = dip_map_src(ty * C::TH * S + hr - d.off, d.Hin, d.pad_mode);
+            const int sc = dip_map_src(tx * C::TW * S + hc - d.off, d.Win, d.pad_mode);
             uok[i] = sr >= 0 && sc >= 0 && ucv;
             uv[i] = *reinterpret_cast<const f32x4w*>(d.x + (uok[i] ? ((size_t)sr * d.Win + sc) * d.Cx + uc : 0));
         }
@@ -217,7 +211,7 @@ bool wthin_shape_ok(int Hout, int Wout, int Cin, int Cout, int ks, int stride) {
     if (ks != 3 && ks != 5) return false;
     if (stride != 1 && stride != 2) return false;
     if (Cin < 8 || Cin > 64 || Cout < 1 || Cout > 64) return false;
-    static const int minpix = getenv("DIP_WGRAD_THIN_MIN_PIXELS") ? atoi(getenv("DIP_WGRAD_THIN_MIN_PIXELS")) : 4096;
+    constexpr int minpix = 4096;      // 64 x 64: below, the generic weight-gradient kernels keep the layer
     return Hout * Wout >= minpix;
 }
 
@@ -226,7 +220,7 @@ int wthin_nsplit(int Hout, int Wout, int Cin, int Cout, int ks, int stride) {
     wthin_blocks(Cin, Cout, stride, &ci, &co);
     const int blocks = dip_cdiv(Cin, 16 * ci) * dip_cdiv(Cout, 16 * co);
     const int nt = dip_cdiv(Wout, 16) * dip_cdiv(Hout, 8);
-    static const int target = getenv("DIP_WGRAD_THIN_WGS") ? atoi(getenv("DIP_WGRAD_THIN_WGS")) : 512;
+    constexpr int target = 512;      // workgroups of a launch
     int n = target / blocks;
     if (n > nt) n = nt;
     if (n < 1) n = 1;

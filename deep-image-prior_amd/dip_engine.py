@@ -149,7 +149,7 @@ class SkipEngine:
         # y are whole lines) -- an experiment of round 6's last session
         self.fuse_bnb_1x1 = os.environ.get("DIP_BNB_FUSE", "0") == "2"
         self.thin_src = os.environ.get("DIP_NO_THIN_SRC") is None
-        # low-resolution layers (<= DIP_SMALL_MAX_PIXELS output pixels): ONE dip_conv_small launch per convolution
+        # low-resolution layers (dip_conv_small_eligible: <= 68 x 68 output pixels): ONE dip_conv_small launch per convolution
         # (conv + in-workgroup split-K + BatchNorm partials; dip_bn_finalize follows) instead of conv + split-K finish +
         # bn_finalize, and data gradient + BatchNorm-backward partials (+ dip_bn_bwd_finalize2) instead of four launches
         # (csrc/conv_small.hip); DIP_CONV_NO_SMALL=1 restores the round-3 lists
@@ -161,27 +161,21 @@ class SkipEngine:
         self.ticket_fin = os.environ.get("DIP_TICKET_FIN") == "1"
         # low-resolution BatchNorm backward as ONE launch (csrc/bn_bwd_one.hip: a workgroup owns four channels of the whole
         # plane, so statistics -> finalise -> apply needs no grid-wide dependency); the library decides per shape
-        # (dip_bn_bwd_one_ok: DIP_BNB_ONE_MAX_PIXELS, 0 = off)
+        # (dip_bn_bwd_one_ok: up to 32 x 32 pixels)
         self.bnb_one = os.environ.get("DIP_BNB_NO_ONE") is None
         self.tail_inline = self.two_streams and os.environ.get("DIP_TAIL_INLINE", "1") != "0"
-        # phase 2 of a BatchNorm backward in the prologue of its apply launch when phase 1 left few partial rows
-        # (dip_bn_bwd_apply_src_fin / _apply_fin; the library decides: dip_bn_bwd_fin_rows_ok, DIP_BNB_FIN_MAX_ROWS)
-        # MEASURED (profiles/r06_ab_bnb_fin_fuse.txt): -8 launches per iteration of the default net, -10 of the 'library' net,
-        # and -0.4 % / -0.5 % it/s -- a dependent 5 us launch costs the chain ~2.5 us, the prologue's rows cost every block
-        # as much.  Opt-in (DIP_BNB_FIN_FUSE=1); parity-tested either way (tests/test_bnone_gpu.py).
-        self.bnb_fin_fuse = os.environ.get("DIP_BNB_FIN_FUSE") == "1"
-        # second bulk stream (round 6): the weight gradients of layers with <= DIP_BULK2_MAX_PIXELS output pixels alternate
+        # (phase 2 of a BatchNorm backward in the prologue of its apply launch was measured at -0.4 % / -0.5 % it/s and removed:
+        # profiles/r06_ab_bnb_fin_fuse.txt -- a dependent 5 us launch costs the chain ~2.5 us, the prologue's rows cost every
+        # block as much)
+        # second bulk stream (round 6): the weight gradients of layers with <= bulk2_max_pixels output pixels alternate
         # between two bulk streams (scratch sets of their own), so that two of these small launches -- none fills the chip --
         # run side by side.  The 'library' net's bulk stream was backlogged: 1.35 ms of weight gradients queued one after the
         # other, the last three still waiting when the main chain had finished (profiles/r06_library_timeline_*.txt)
         # Only for nets WITHOUT big MFMA-bound layers: with them (the default / kate nets: 128 x 128-channel 3x3 convs at
         # >= 256 x 256) the one bulk stream is not backlogged and a second one costs 2 % (more fork events on the main
         # chain, two MFMA-bound launches side by side gain nothing): library 370.6 -> 383.0 it/s, default 182.4 -> 178.1
-        # (profiles/r06_ab_bulk2.txt).  DIP_BULK2_MAX_PIXELS overrides (0 = off).
-        self.bulk2_max_pixels = 0
-        if self.two_streams:
-            env = os.environ.get("DIP_BULK2_MAX_PIXELS")
-            self.bulk2_max_pixels = int(env) if env is not None else -1        # -1: decided per plan (_build_plan)
+        # (profiles/r06_ab_bulk2.txt).  0 = off; -1: decided per plan (_begin_plan)
+        self.bulk2_max_pixels = -1 if self.two_streams else 0
         self._bulk2, self._bulk_flip = set(), False
         # bf16 matrix pipe for the big 3x3 layers (csrc/conv_bf3.hip: fp32 operands as three exact bf16 terms, the
         # cross products accumulated in fp32): the library decides per descriptor (DIP_CONV_BF3=8 | 9 | 6 | 0), the engine only
@@ -323,17 +317,12 @@ class SkipEngine:
                 r.fwd3_off = r.dgrad3_off = -1
                 nchF, nchD = (round_up(r.Cin, 4) + 15) // 16, (round_up(r.Cout, 4) + 15) // 16
                 CoutP, CinP = round_up(r.Cout, 32), round_up(r.Cin, 32)
-                # (1x1 layers, round 6, opt-in -- measured slower per iteration: conv_bf3_k1_kernel takes them from 256 tiles,
-                # whole 16-channel chunks on both sides)
-                k1 = (os.environ.get("DIP_CONV_BF3_1X1") == "1" and r.ks == 1 and r.Cin % 16 == 0 and r.Cout % 16 == 0
-                      and min(r.Cin, r.Cout) >= 128)
-                if (r.ks == 3 or k1) and r.stride == 1 and not r.name.endswith(".down_ds"):
-                    kk = r.ks * r.ks
+                if r.ks == 3 and r.stride == 1 and not r.name.endswith(".down_ds"):
                     r.fwd3_off = off3
-                    off3 += kk * nchF * 3 * CoutP * 16
+                    off3 += 9 * nchF * 3 * CoutP * 16
                     r.dgrad3_off = off3
-                    off3 += kk * nchD * 3 * CinP * 16
-                    max3 = max(max3, kk * 16 * (nchF * CoutP + nchD * CinP))
+                    off3 += 9 * nchD * 3 * CinP * 16
+                    max3 = max(max3, 9 * 16 * (nchF * CoutP + nchD * CinP))
                 recs3[k] = N.DipPackRec3(w_off=r.w_off, fwd_off=r.fwd3_off, dgrad_off=r.dgrad3_off, Cout=r.Cout, Cin=r.Cin,
                                          KS=r.ks, nchF=nchF, CoutP32=CoutP, nchD=nchD, CinP32=CinP)
             self.packed3 = self._dalloc(max(off3, 8), torch.int16, zero=True)
@@ -391,7 +380,7 @@ class SkipEngine:
 
     def _begin_plan(self, H, W, Cin_img):
         """What the plan of every backbone starts with: the shape, no compiled lists, no buffers, scratch sizes reset, and
-        the second bulk stream iff the net has no big layer at this input size (unless DIP_BULK2_MAX_PIXELS decided)."""
+        the second bulk stream iff the net has no big layer at this input size (unless bulk2_max_pixels was set to 0)."""
         self.H, self.W, self.Cimg = H, W, Cin_img
         self._clists = {}
         self._reset_sizing()
@@ -834,27 +823,22 @@ class SkipEngine:
         of phase 3."""
         return (_ptr(self.grads, bn.gamma_off), _ptr(self.grads, bn.beta_off), _ptr(bn.coef))
 
-    def _emit_bnb_apply(self, a: Act, dz, ops, src=None, partials=None):
+    def _emit_bnb_apply(self, a: Act, dz, ops, src=None):
         """Phase 3 of the BatchNorm backward of `a` into dz.  src: the gradient source the masked gradient is recomputed
-        from; None: dz holds it already (the adjoint of the up-sampling wrote it).  partials = (scratch, rows): phase 2 rides
-        in the launch's prologue -- every block reduces the few partial rows, no finalisation launch."""
+        from; None: dz holds it already (the adjoint of the up-sampling wrote it)."""
         bn, lib = a.bn, self.lib
-        if partials is None:
-            fns, fin = (lib.dip_bn_bwd_apply, lib.dip_bn_bwd_apply_src), (_ptr(bn.coef),)
-        else:
-            fns = (lib.dip_bn_bwd_apply_fin, lib.dip_bn_bwd_apply_src_fin)
-            fin = (_ptr(partials[0]), partials[1], *self._dparams(bn))
         if src is None:
-            args = (_ptr(dz), a.Cs, _ptr(a.buf), a.Cs, a.H * a.W, a.C, _ptr(bn.state), bn.Cs, *fin)
+            fn = lib.dip_bn_bwd_apply
+            args = (_ptr(dz), a.Cs, _ptr(a.buf), a.Cs, a.H * a.W, a.C, _ptr(bn.state), bn.Cs, _ptr(bn.coef))
         else:
-            args = (C.byref(src), *self._act_args(a), *fin, _ptr(dz), a.Cs)
-        ops.append((fns[src is not None], args, "bnb_apply:" + bn.name))
+            fn = lib.dip_bn_bwd_apply_src
+            args = (C.byref(src), *self._act_args(a), _ptr(bn.coef), _ptr(dz), a.Cs)
+        ops.append((fn, args, "bnb_apply:" + bn.name))
 
     def _emit_bnb_fin_apply(self, a: Act, scratch, rows, dz, ops, src=None):
-        """Phases 2 and 3 of the BatchNorm backward of `a` from the `rows` partial rows that phase 1 left in scratch."""
+        """Phases 2 and 3 of the BatchNorm backward of `a` from the `rows` partial rows that phase 1 left in scratch:
+        finalise, then apply."""
         bn = a.bn
-        if self._fin_rows_ok(rows, a.C):
-            return self._emit_bnb_apply(a, dz, ops, src, (scratch, rows))
         ops.append((self.lib.dip_bn_bwd_finalize, (_ptr(scratch), rows, bn.Cs, bn.C, a.H * a.W, *self._dparams(bn)),
                     "bnb_fin:" + bn.name))
         self._emit_bnb_apply(a, dz, ops, src)
@@ -895,17 +879,11 @@ class SkipEngine:
             # phase 1 already ran in the epilogue of the data-gradient launch(es) that produced g (_fuse_bnb_into: the partial
             # rows are in the main stream's scratch, the thin columns' in "bwd3")
             rows, rows_lo, c_lo = fused
-            if c_lo == 0 and self._fin_rows_ok(rows, a.C):
-                self._emit_bnb_apply(a, dz, ops, src, (scratch, rows))
-                return dz
             thin = self._scratch("bwd3", rows_lo * 2 * bn.Cs) if c_lo else None
             ops.append((lib.dip_bn_bwd_finalize2, (_ptr(scratch), rows, _ptr(thin), rows_lo, c_lo, bn.Cs, bn.C, a.H * a.W,
                                                    *self._dparams(bn)), "bnb_fin:" + bn.name))
             self._emit_bnb_apply(a, dz, ops, src)
         return dz
-
-    def _fin_rows_ok(self, rows, Cc) -> bool:
-        return self.bnb_fin_fuse and bool(self.lib.dip_bn_bwd_fin_rows_ok(rows, Cc))
 
     def _bnb_one_ok(self, a: Act) -> bool:
         return self.bnb_one and a.bn is not None and bool(self.lib.dip_bn_bwd_one_ok(a.H * a.W, a.C))

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DIP_ABI_VERSION 8
+#define DIP_ABI_VERSION 9
 
 #define DIP_PAD_ZERO 0
 #define DIP_PAD_REFLECT 1
@@ -275,8 +275,7 @@ int dip_conv_plan_dil2(int Hout, int Wout, int Cin, int Cout, int ks, int* kspli
  * 4 = conv_igemm_dma_kernel in phase mode (dil == 2: data gradient of a stride-2 3x3 convolution),
  * 5 = conv_igemm_dma_kernel in strided-forward mode (3x3, stride 2: the input split by pixel parity),
  * 6 = conv1x1_res_kernel (1x1, 128 -> 97..128 channels, >= 256x256 pixels: persistent workgroups, weights in registers),
- * 7 = conv_bf3_kernel (3x3 stride 1 on the bf16 matrix pipe; with DIP_CONV_BF3_1X1=1 also 1x1 layers from 256 tiles:
- * conv_bf3_k1_kernel, measured slower per iteration and off by default), 8 = conv_thin_kernel (<= 64 channels in and out, 3x3 / 5x5,
+ * 7 = conv_bf3_kernel (3x3 stride 1 on the bf16 matrix pipe), 8 = conv_thin_kernel (<= 64 channels in and out, 3x3 / 5x5,
  * 16x16x4 MFMA tiles, all taps' weights LDS-resident: the high-resolution layers of the narrow nets) */
 int dip_conv_variant(const DipConvDesc* d);
 /* The two launches behind variant 3, exported so that a caller can put them on DIFFERENT streams (they
@@ -286,7 +285,7 @@ int dip_conv_variant(const DipConvDesc* d);
 int dip_conv_thin4(const DipConvDesc* d, int ncols, void* stream);
 int dip_conv_igemm_dma_cols(const DipConvDesc* d, int n_base, void* stream);
 /* Thin layers (round 6, csrc/conv_thin.hip): 3x3 / 5x5, stride 1 / 2 (forward) or the stride-1 data gradient, <= 64 input
- * and output channels, more than DIP_THIN_MIN_PIXELS (4625) output pixels -- the 16 / 32 / 64-channel layers of the
+ * and output channels, at least 4625 output pixels -- the 16 / 32 / 64-channel layers of the
  * 'library' inpainting net (inpainting.ipynb:222-232) and the snail net (denoising.ipynb:143-150) at their high
  * resolutions; same contract as dip_conv_igemm (which dispatches to it: dip_conv_variant == 8), one pass, stats rows =
  * dip_conv_ntiles.  dip_conv_thin_shape_ok: the shape part of the eligibility (what dip_conv_plan knows). */
@@ -301,7 +300,7 @@ int dip_conv_thin_shape_ok(int Hout, int Wout, int Cin, int Cout, int ks, int st
  * partials ([rows][2][bnb_Cs], for dip_bn_bwd_finalize2 with nblk_lo = 0); any 1..160 output columns (no conv_thin4 side
  * launch).  1x1 / 3x3, stride 1 / 2, dil 1 / 2 (dil == 2: per output-parity class, only the taps that hit non-zero
  * positions), every padding mode and activation; d->ksplit / d->ws are ignored.
- * dip_conv_small_eligible: the shape is served AND Hout * Wout <= DIP_SMALL_MAX_PIXELS (default 4624 = 68 x 68);
+ * dip_conv_small_eligible: the shape is served AND Hout * Wout <= 4624 (= 68 x 68);
  * dip_conv_small_rows: rows of the partial buffers (0: shape not served). */
 int dip_conv_small(const DipConvDesc* d, void* stream);
 int dip_conv_small_eligible(const DipConvDesc* d);
@@ -312,8 +311,8 @@ int dip_conv_small_rows(const DipConvDesc* d);
  * what the ring of the padded domain folds onto the frame rows 1, H-2 / columns 1, W-2 -- per frame pixel the gradient of
  * the <= 3 ring positions that mirror onto it, accumulated into y.  `d` = the interior descriptor (x = dy [H][W],
  * y = gradient [H][W][Cy], ks 3, stride 1, dil 1, off 1, DIP_PAD_ZERO, no transform / bias / stats).  The gradient buffer
- * then needs no fold (DipGradSrc.pad = 0).  dip_conv_dgrad_ring_ok: shape served and H * W <= DIP_DGRAD_RING_MAX
- * (default 300000: up to 512 x 512). */
+ * then needs no fold (DipGradSrc.pad = 0).  dip_conv_dgrad_ring_ok: shape served and H * W <= 300000
+ * (up to 512 x 512). */
 int dip_conv_dgrad_ring(const DipConvDesc* d, void* stream);
 int dip_conv_dgrad_ring_ok(const DipConvDesc* d);
 /* bf16-pipe convolution (see DipConvDesc.wp3): eligibility of `d`, the launch of columns [n_base, n_base + ncols) and the
@@ -357,8 +356,7 @@ int dip_wgrad_bf3(const DipWgradDesc* d, void* stream);
 int dip_conv_wgrad_tail(const DipWgradDesc* d, void* stream);
 /* The same rows as a streaming kernel (round 6, wgrad_tail.hip; dip_conv_wgrad_tail dispatches to it): (tap, channel) packed
  * into the rows of the fp32 MFMA, K = pairs of output pixels straight from global memory, one pass over dy, the slabs of
- * `d->nsplit` walkers written like the bf16-pipe kernel's.  _ok: 3x3, stride 1, 1..4 channels behind whole 32-channel chunks
- * (DIP_WGRAD_TAIL_OLD=1 switches it off). */
+ * `d->nsplit` walkers written like the bf16-pipe kernel's.  _ok: 3x3, stride 1, 1..4 channels behind whole 32-channel chunks. */
 int dip_wgrad_tail_stream_ok(const DipWgradDesc* d);
 int dip_wgrad_tail_stream(const DipWgradDesc* d, void* stream);
 /* Thin layers (round 6, csrc/wgrad_thin.hip): 3x3 / 5x5, stride 1 / 2, 8..64 input channels, <= 64 output channels, >= 4096
@@ -443,24 +441,13 @@ int dip_bn_bwd_apply(float* dz, int Cdz, const float* y, int Cy, int npix, int C
 int dip_bn_bwd_apply_src(const DipGradSrc* src, const float* y, int H, int W, int Cy, int C,
                          const float* state, int Cs, float slope, const float* coef, float* dy, int Cdy,
                          void* stream);
-/* Phases 2 + 3 in one launch (round 6): every block of the apply launch reduces the `nrows` partial rows [nrows][2][Cs] of
- * phase 1 for itself in its prologue (fp64, fixed order: the same k1, k2 in every block) and block 0 writes dgamma, dbeta
- * (may be NULL) and coef -- no dip_bn_bwd_finalize launch in the dependent chain.  Same reference ops as above.
- * dip_bn_bwd_fin_rows_ok: 1 when the engine should use the form (nrows <= DIP_BNB_FIN_MAX_ROWS, default 320: every block
- * reads nrows * C * 8 bytes from L2). */
-int dip_bn_bwd_fin_rows_ok(int nrows, int C);
-int dip_bn_bwd_apply_fin(float* dz, int Cdz, const float* y, int Cy, int npix, int C, const float* state, int Cs,
-                         const float* partials, int nrows, float* dgamma, float* dbeta, float* coef, void* stream);
-int dip_bn_bwd_apply_src_fin(const DipGradSrc* src, const float* y, int H, int W, int Cy, int C, const float* state, int Cs,
-                             float slope, const float* partials, int nrows, float* dgamma, float* dbeta, float* coef,
-                             float* dy, int Cdy, void* stream);
 /* The three phases in ONE launch for low-resolution activations (round 6; csrc/bn_bwd_one.hip): a workgroup owns four
  * channels of the whole H x W plane, so S1 = sum dz and S2 = sum dz * xhat are workgroup-local (per-thread fp32 sums, a
  * fixed-order fp64 reduction) and dy = a * (du * act'(a*y+b) - S1/N - xhat * S2/N) follows in the same launch; dgamma,
  * dbeta and coef [2][Cs] are written as dip_bn_bwd_finalize writes them (each may be NULL).  Same reference ops as
  * dip_bn_bwd_stats / _finalize / _apply_src (autograd NativeBatchNormBackward + LeakyReluBackward of
- * models/common.py:82,96).  dip_bn_bwd_one_ok: 1 when the engine should use this form (npix <= DIP_BNB_ONE_MAX_PIXELS,
- * default 1024 = 32 x 32: above that a 4-channel slice of the plane costs 8x its bytes in L1 fills; 0 switches it off). */
+ * models/common.py:82,96).  dip_bn_bwd_one_ok: 1 when the engine should use this form (npix <= 1024
+ * = 32 x 32: above that a 4-channel slice of the plane costs 8x its bytes in L1 fills). */
 int dip_bn_bwd_one_ok(int npix, int C);
 int dip_bn_bwd_one(const DipGradSrc* src, const float* y, int H, int W, int Cy, int C, const float* state, int Cs,
                    float slope, float* dy, int Cdy, float* dgamma, float* dbeta, float* coef, void* stream);

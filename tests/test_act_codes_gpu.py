@@ -196,10 +196,3 @@ def test_bn_bwd_one(dev, Cc, Hh, Ww, P, code):
 @pytest.mark.parametrize("ns,nd,Hh,Ww,mode,od", [(4, 16, 25, 39, "bilinear", (0, 0)), (4, 128, 128, 128, "bilinear", (0, 0))])
 def test_upsample_bwd_one(dev, ns, nd, Hh, Ww, mode, od, code):
     T1.test_upsample_bwd_one_matches_autograd(dev, ns, nd, Hh, Ww, mode, od, slope=code)
-
-
-@codes
-@pytest.mark.parametrize("Cc,Hh,Ww,P", [(16, 19, 23, 1), (64, 56, 88, 2)])
-def test_bn_bwd_finalise_in_the_apply_prologue(dev, Cc, Hh, Ww, P, code):
-    """dip_bn_bwd_apply_src_fin / dip_bn_bwd_apply_fin."""
-    T1.test_bn_bwd_finalise_in_the_apply_prologue(dev, Cc, Hh, Ww, P, code)

@@ -45,7 +45,7 @@ def test_symbols_header_and_descriptor(built):
             names += [re.split(r"[\s\*]+", first.strip())[-1]] + [r.strip().lstrip("*") for r in rest]
     assert names == fields
     assert "dip_early_stop_emv_dev" in N.EXPORTS and hasattr(built, "dip_early_stop_emv_dev")
-    assert built.dip_abi_version() == N.ABI_VERSION == 8            # a new entry point, a new struct, no existing one changed
+    assert built.dip_abi_version() == N.ABI_VERSION == 9            # a new entry point, a new struct, no existing one changed
     assert ctypes.sizeof(N.DipEarlyStopDesc) == 96
     for name in ("GroupedEarlyStopMonitor", "early_stop_emv_descriptor", "early_stop_state_fill"):
         assert callable(getattr(FM, name)), name

@@ -52,7 +52,7 @@ def test_symbols_header_and_descriptor(built):
     assert names == fields
     for name in ("dip_early_stop_dev", "dip_early_stop_keep"):
         assert name in N.EXPORTS and hasattr(built, name)
-    assert built.dip_abi_version() == N.ABI_VERSION == 8            # new entry points, a new struct, no existing one changed
+    assert built.dip_abi_version() == N.ABI_VERSION == 9            # new entry points, a new struct, no existing one changed
     assert ctypes.sizeof(N.DipFitMonitorDesc) == 104 and ctypes.sizeof(N.DipSRMonitorDesc) == 88
     assert ctypes.sizeof(N.DipRestoreMonitorDesc) == 104
     for name in ("EarlyStopMonitor", "early_stop_state", "early_stop_descriptor", "early_stop_launches"):

@@ -26,7 +26,6 @@ DEFAULT_KW = dict(skip_n33d=128, skip_n33u=128, skip_n11=4, num_scales=5)
 # variables of the same names once per process, so the environment is not used)
 SWITCHES = {
     "ticket": dict(ticket_fin=True, bnb_one=False),
-    "finfuse": dict(bnb_fin_fuse=True, bnb_one=False),
     "fusebnb": dict(fuse_bnb=True),
     "fuse1x1": dict(fuse_bnb_1x1=True, thin_src=False),
     "noone": dict(bnb_one=False),
@@ -43,8 +42,8 @@ CASES.update({f"{n}@{h}x{w}+{s}": (n, (h, w), s) for s in SWITCHES for n, (h, w)
 ENTRY_POINTS = frozenset("""dip_bn_finalize dip_conv_small dip_conv_igemm dip_avgpool2_fwd dip_maxpool2_fwd dip_upcat_fwd
     dip_upcat_fwd_fin dip_conv_wgrad dip_wgrad_reduce dip_conv_thin4 dip_conv_igemm_dma_cols dip_conv_dgrad_ring dip_bn_bwd_one
     dip_bn_bwd_stats dip_bn_bwd_stats_fin dip_bn_bwd_finalize dip_bn_bwd_finalize2 dip_bn_bwd_apply_src
-    dip_bn_bwd_apply_src_fin dip_upsample_bwd_one dip_upsample_bwd_stats dip_upsample_bwd_stats_crop
-    dip_upsample_bwd_stats_crop_fin dip_bn_bwd_apply dip_bn_bwd_apply_fin dip_fold_to_nhwc dip_avgpool2_bwd dip_maxpool2_bwd
+    dip_upsample_bwd_one dip_upsample_bwd_stats dip_upsample_bwd_stats_crop
+    dip_upsample_bwd_stats_crop_fin dip_bn_bwd_apply dip_fold_to_nhwc dip_avgpool2_bwd dip_maxpool2_bwd
     dip_res_join_fwd dip_res_join_bwd""".split())
 
 

@@ -23,11 +23,32 @@ def test_cabi_exports_every_declared_symbol(built):
     L = ctypes.CDLL(dip_native.LIB_PATH)
     for name in declared:
         assert hasattr(L, name), name
-    assert built.dip_abi_version() == dip_native.ABI_VERSION == 8
+    assert built.dip_abi_version() == dip_native.ABI_VERSION == 9
     # struct layouts agree with the header's field order (sizes on LP64)
     assert ctypes.sizeof(dip_native.DipTransform) == 24
     assert ctypes.sizeof(dip_native.DipGradSrc) == 56     # + the crop window of round 3, the thin 1x1 conv of round 6
     assert ctypes.sizeof(dip_native.DipPackRec) == 56
+
+
+def test_environment_switches_are_the_documented_ones():
+    """The DIP_* variables the package reads (getenv in csrc/, os.environ in the Python modules) are exactly the rows of the
+    table "Environment switches" of INTEGRATION.md: no switch appears or lingers unlisted."""
+    pkg = os.path.join(ROOT, "deep-image-prior_amd")
+    read = set()
+    for d, dirs, files in os.walk(pkg):
+        dirs[:] = [x for x in dirs if x not in ("build", "lib", "__pycache__")]
+        for f in files:
+            if f.endswith((".hip", ".h", ".py")):
+                for line in open(os.path.join(d, f), errors="replace"):
+                    if "getenv" in line or "environ" in line:
+                        read.update(re.findall(r'"(DIP_[A-Z0-9_]+)"', line))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("Environment switches"):]
+    rows = re.findall(r"^\| `(DIP_[A-Z0-9_]+)` \|([^|]+)\|([^|]+)\|$", table, flags=re.M)
+    listed = [r[0] for r in rows]
+    assert len(listed) == len(set(listed)), sorted(n for n in set(listed) if listed.count(n) > 1)
+    assert read == set(listed), (sorted(read - set(listed)), sorted(set(listed) - read))
+    assert all(what.strip() and test.strip() for _, what, test in rows)
 
 
 def test_state_dict_names_and_shapes_match_oracle_spec():

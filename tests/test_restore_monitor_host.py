@@ -73,7 +73,7 @@ def test_symbols_header_and_descriptor(built):
     assert N.DipRestoreMonitorDesc.state.offset == N.DipFitMonitorDesc.state.offset == 96
     for name in ("dip_restore_monitor", "dip_restore_monitor_dev"):
         assert name in N.EXPORTS and hasattr(built, name)
-    assert built.dip_abi_version() == N.ABI_VERSION == 8          # new entry points, a new struct, no existing one changed
+    assert built.dip_abi_version() == N.ABI_VERSION == 9          # new entry points, a new struct, no existing one changed
     assert ctypes.sizeof(N.DipFitMonitorDesc) == 104 and ctypes.sizeof(N.DipSRMonitorDesc) == 88
     # the three places that said FitMonitor covers restoration.ipynb:192-211 point at the new entry points
     import dip_optim

@@ -70,7 +70,7 @@ def test_symbols_header_and_descriptor(built):
     assert names == [f[0] for f in N.DipSRMonitorDesc._fields_]
     for name in ("dip_sr_monitor", "dip_sr_monitor_dev"):
         assert name in N.EXPORTS and hasattr(built, name)
-    assert built.dip_abi_version() == N.ABI_VERSION == 8          # new entry points, a new struct, no existing one changed
+    assert built.dip_abi_version() == N.ABI_VERSION == 9          # new entry points, a new struct, no existing one changed
     assert ctypes.sizeof(N.DipFitMonitorDesc) == 104 and ctypes.sizeof(N.DipSRLossDesc) == 96
 
 

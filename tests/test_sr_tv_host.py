@@ -31,7 +31,7 @@ def test_header_binding_and_command_list_know_the_entry_points(built):
         assert built.dip_list_fn_nargs(fid) == nargs == len(N._SIGS[name][1]), name
     assert built.dip_list_fn_id(b"dip_sr_tv_nblk") == -1
     # what is pinned stays: new symbols and a new struct only
-    assert built.dip_abi_version() == N.ABI_VERSION == 8
+    assert built.dip_abi_version() == N.ABI_VERSION == 9
     assert ctypes.sizeof(N.DipSRLossDesc) == 96
     for name in ("dip_sr_loss_fwd", "dip_sr_loss_bwd"):
         assert built.dip_list_fn_id(name.encode()) >= 0

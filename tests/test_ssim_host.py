@@ -85,7 +85,7 @@ def test_symbols_header_descriptor_and_nblk(built):
     names = [n.strip(" *") for decl in fields.split(";") if decl.strip() for n in decl.strip().split(" ", 1)[1].split(",")]
     names = [n.split("*")[-1].strip() for n in names]
     assert names == [f for f, _ in N.DipSsimDesc._fields_] and "sizeof(DipSsimDesc) == 88" in hdr
-    assert N.ABI_VERSION == 8 and built.dip_list_fn_id(b"dip_ssim_dev") >= 0
+    assert N.ABI_VERSION == 9 and built.dip_list_fn_id(b"dip_ssim_dev") >= 0
     th, tw = 16, 64
     for C, H, W in [(1, 11, 11), (3, th + 10, tw + 10), (3, th + 11, tw + 11), (4, 33, 129), (3, 512, 512)]:
         assert built.dip_ssim_nblk(C, H, W) == C * -(-(H - 10) // th) * -(-(W - 10) // tw)
