@@ -241,10 +241,9 @@ __global__ __launch_bounds__(256) void loss_head_bwd_kernel(const DipLossHeadDes
 }
 
 // ---------------------------------------------------------------- device-side iteration state
-template <bool GRP = false>
-__global__  void adam_tick_kernel(DipIterState* st_, double lr, double beta1, double beta2, const DipGrpArg<GRP> grp) {
-    DIP_GRP_PTR(DipIterState*, st);
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// t <- t + 1 and the two step-dependent scalars: what adam_tick_kernel (lr by value) and adam_tick_dev_kernel (lr in device
+// memory) both run, so the two cannot drift apart
+__device__ __forceinline__ void adam_tick_body(DipIterState* st, double lr, double beta1, double beta2) {
     const unsigned long long step = st->step + 1ull;
     st->step = step;
     // scalar prep as torch/optim/adam.py (_single_tensor_adam), in double
@@ -252,6 +251,24 @@ __global__  void adam_tick_kernel(DipIterState* st_, double lr, double beta1, do
     const double bc2 = 1.0 - pow(beta2, (double)step);
     st->step_size = (float)(lr / bc1);
     st->bc2_sqrt = (float)sqrt(bc2);
+}
+
+template <bool GRP = false>
+__global__  void adam_tick_kernel(DipIterState* st_, double lr, double beta1, double beta2, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(DipIterState*, st);
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    adam_tick_body(st, lr, beta1, beta2);
+}
+
+// lr read from device memory: a grouped pointer like st, so every instance of a group steps with the lr of its own slab row,
+// and a setter rewrites it in stream order under a captured graph
+template <bool GRP = false>
+__global__  void adam_tick_dev_kernel(DipIterState* st_, const double* __restrict__ lr_dev_, double beta1, double beta2,
+                                      const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(DipIterState*, st);
+    DIP_GRP_PTR(const double*, lr_dev);
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    adam_tick_body(st, *lr_dev, beta1, beta2);
 }
 
 template <bool GRP = false>
@@ -320,6 +337,15 @@ extern "C" int dip_loss_head_bwd(const DipLossHeadDesc* dp, const float* gscale,
 
 extern "C" int dip_adam_tick(DipIterState* st, double lr, double beta1, double beta2, void* stream) {
     dip_launch_pair<DIP_FAM_LOSS>(adam_tick_kernel<false>, adam_tick_kernel<true>, dim3(1), dim3(1), 0, (hipStream_t)stream, st, lr, beta1, beta2);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_adam_tick_dev(DipIterState* st, const double* lr_dev, double beta1, double beta2, void* stream) {
+    if (st == nullptr) DIP_FAIL("adam_tick_dev: iteration state is NULL");
+    if (lr_dev == nullptr) DIP_FAIL("adam_tick_dev: lr pointer is NULL");
+    dip_launch_pair<DIP_FAM_LOSS>(adam_tick_dev_kernel<false>, adam_tick_dev_kernel<true>, dim3(1), dim3(1), 0, (hipStream_t)stream, st,
+                                  lr_dev, beta1, beta2);
     DIP_CHECK_LAUNCH();
     return 0;
 }

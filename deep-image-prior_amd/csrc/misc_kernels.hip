@@ -211,13 +211,20 @@ __device__ __forceinline__ void philox_normals4(uint64_t ctr, uint64_t seed, flo
 }
 
 // SEED_DEV: the seed, too, lives in device memory (offset_dev[1]): grouped fits with one stream per instance
-template <bool GRP = false, bool SEED_DEV = false>
+// SIGMA_DEV: so does sigma -- the argument is then a pointer to one float, a grouped pointer like the others, so every instance
+// of a group reads the level of its own slab row and a setter rewrites it in stream order under a captured graph.  The
+// parameter's TYPE follows the flag: the SIGMA_DEV = false instantiations keep their signature and their code.
+template <bool GRP = false, bool SEED_DEV = false, bool SIGMA_DEV = false>
 __global__ __launch_bounds__(256) void noise_axpy_kernel(const float* __restrict__ z_, float* __restrict__ out_,
-                                                         int64_t n, float sigma, uint64_t seed, uint64_t offset,
+                                                         int64_t n, std::conditional_t<SIGMA_DEV, const float*, float> sigma_,
+                                                         uint64_t seed, uint64_t offset,
                                                          const uint64_t* __restrict__ offset_dev_, const DipGrpArg<GRP> grp) {
     DIP_GRP_PTR(const float*, z);
     DIP_GRP_PTR(float*, out);
     DIP_GRP_PTR(const uint64_t*, offset_dev);
+    float sigma;
+    if constexpr (SIGMA_DEV) sigma = *(GRP ? dip_gshift(sigma_, dip_grp_off<GRP>(grp)) : sigma_);
+    else sigma = sigma_;
     if (offset_dev != nullptr) offset = *offset_dev;              // device-side stream position (graph replay)
     if constexpr (SEED_DEV) seed = offset_dev[1];
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one Philox block = 4 normals
@@ -606,6 +613,37 @@ extern "C" int dip_noise_axpy_dev2(const float* z, float* out, int64_t n, float 
                                   (hipStream_t)stream, z, out, n, sigma, (uint64_t)0, (uint64_t)0, (const uint64_t*)state_dev);
     DIP_CHECK_LAUNCH();
     return dip_counter_add(state_dev, (uint64_t)quads, stream);
+}
+
+// dip_noise_axpy_dev2 with sigma in device memory too (a grouped pointer: one level per instance), and the solo counterpart
+// of dip_noise_axpy_dev: the seed by value, the offset and sigma on the device.  Both are SIGMA_DEV instantiations of
+// noise_axpy_kernel: one body.
+extern "C" int dip_noise_axpy_dev3(const float* z, float* out, int64_t n, const float* sigma_dev, uint64_t* state_dev,
+                                   void* stream) {
+    if (n <= 0) DIP_FAIL("noise_axpy_dev3: n must be positive");
+    if (state_dev == nullptr) DIP_FAIL("noise_axpy_dev3: state pointer is NULL");
+    if (sigma_dev == nullptr) DIP_FAIL("noise_axpy_dev3: sigma pointer is NULL");
+    if (z == nullptr || out == nullptr) DIP_FAIL("noise_axpy_dev3: z or out is NULL");
+    const int64_t quads = (n + 3) / 4;
+    dip_launch_pair<DIP_FAM_LOSS>(noise_axpy_kernel<false, true, true>, noise_axpy_kernel<true, true, true>,
+                                  dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, out, n, sigma_dev,
+                                  (uint64_t)0, (uint64_t)0, (const uint64_t*)state_dev);
+    DIP_CHECK_LAUNCH();
+    return dip_counter_add(state_dev, (uint64_t)quads, stream);
+}
+
+extern "C" int dip_noise_axpy_dev1s(const float* z, float* out, int64_t n, const float* sigma_dev, uint64_t seed,
+                                    uint64_t* offset_dev, void* stream) {
+    if (n <= 0) DIP_FAIL("noise_axpy_dev1s: n must be positive");
+    if (offset_dev == nullptr) DIP_FAIL("noise_axpy_dev1s: offset pointer is NULL");
+    if (sigma_dev == nullptr) DIP_FAIL("noise_axpy_dev1s: sigma pointer is NULL");
+    if (z == nullptr || out == nullptr) DIP_FAIL("noise_axpy_dev1s: z or out is NULL");
+    const int64_t quads = (n + 3) / 4;
+    dip_launch_pair<DIP_FAM_LOSS>(noise_axpy_kernel<false, false, true>, noise_axpy_kernel<true, false, true>,
+                                  dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, out, n, sigma_dev,
+                                  seed, (uint64_t)0, (const uint64_t*)offset_dev);
+    DIP_CHECK_LAUNCH();
+    return dip_counter_add(offset_dev, (uint64_t)quads, stream);
 }
 
 namespace {

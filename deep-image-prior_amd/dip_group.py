@@ -116,6 +116,18 @@ instance is bit-identical to its solo NativeIteration fit with the same seeds (t
 
     g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, weight_decay=5e-8, param_noise_std=[1e-4, 2e-4, 4e-4])
 
+Learning-rate and input-noise sweeps: `lr=[B floats]` and / or `reg_noise_std=[B floats]` (a float is the group above, launch
+for launch and byte for byte of slab).  A list puts the values into the slab -- one fp64 row `lr`, one fp32 row `reg_std`, behind
+everything else the group owns, so no other row moves -- and ONE grouped dip_adam_tick_dev / dip_noise_axpy_dev3 stands where
+dip_adam_tick / dip_noise_axpy_dev2 stood, inside the bracket and the ONE hipGraph; every instance reads the scalar of its own
+row.  g.set_lr(list) / g.set_reg_noise_std(list) rewrite the rows in stream order (a schedule: run(k); set_lr([lr] * B);
+run(k)), without a re-capture.  A construction list that mixes zero and positive noise levels is refused (a solo fit at level 0
+feeds `saved` itself; on the noise path a -0.0 of the input comes out as +0.0); all zeros is the float 0; the setter may take an
+instance to 0 (saved + 0 * N).  Every instance is bit-identical to its solo NativeIteration fit with FusedAdam(lr=lr[b]) and
+RegNoise(std[b], seeds[b]) (tests/test_sweep_fit_gpu.py).
+
+    g = GroupedFits(nets, [z] * B, [img] * B, lr=[0.01, 0.001, 0.1], reg_noise_std=[1/30, 1/20, 0.03])
+
 There is no CPU or per-instance fallback here: the library must be loaded, and an architecture / size mismatch raises.
 """
 from __future__ import annotations
@@ -169,7 +181,10 @@ class GroupedFits:
                  early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None, ssim=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
-        noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  exp_weight: None = no moving average of the output;
+        noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  lr / reg_noise_std: one float, or B floats = a sweep: the
+        values become per-instance rows of the slab (`lr` fp64, `reg_std` fp32, behind everything else) read by ONE grouped
+        dip_adam_tick_dev / dip_noise_axpy_dev3; set_lr / set_reg_noise_std rewrite them.
+        exp_weight: None = no moving average of the output;
         ema_init 'first' = out_avg starts as the first output (denoising.ipynb:214-215), 'zeros' = starts at 0.
         downsamplers: None = the denoising / inpainting closure; B fixed-taps Downsamplers of one (k, factor, pad) = the
         super-resolution closure, targets = the LR images [1,C,Ho,Wo], no masks.
@@ -204,6 +219,8 @@ class GroupedFits:
             weight_decay, param_noise_std, param_noise_seeds, B, [int(s) for s in (seeds if seeds is not None else range(B))])
         # (explicit zeros are the defaults: the launch list and the slab of a group without SGLD)
         self.sgld = self.weight_decay != 0.0 or any(s != 0.0 for s in self.param_noise_std) or param_noise_seeds is not None
+        # (a float: today's group; a list: the values are rows of the slab)
+        lr, reg_noise_std = self._check_sweep(lr, "lr", B), self._check_sweep(reg_noise_std, "reg_noise_std", B)
         engs = [getattr(n, "__dict__", {}).get("_dip_engine") for n in nets]
         if any(e is None or isinstance(e, Exception) for e in engs):
             raise RuntimeError("dip-amd: GroupedFits needs nets built by models.skip.skip()")
@@ -220,7 +237,9 @@ class GroupedFits:
         self.B, self.nets, self.device = B, list(nets), device
         self.eng = eng = engs[0]
         self.lib = N.lib()
-        self.lr, self.std = float(lr), float(reg_noise_std)
+        self.lr, self.std = lr, reg_noise_std
+        self._lr_rows, self._std_rows = isinstance(lr, list), isinstance(reg_noise_std, list)
+        self._noisy = self._std_rows or self.std > 0
         self.exp_weight = None if exp_weight is None else float(exp_weight)
         if ema_init not in ("first", "zeros"):
             raise ValueError("GroupedFits: ema_init is 'first' or 'zeros'")
@@ -297,6 +316,10 @@ class GroupedFits:
                     self._inst(ex["rng"], b).copy_(torch.tensor([0, self.seeds[b]], dtype=torch.int64))
                     if self.sgld:
                         self._inst(ex["sgld"], b).copy_(self._sgld_state(b))
+                    if self._lr_rows:
+                        self._inst(ex["lr"], b).fill_(self.lr[b])
+                    if self._std_rows:
+                        self._inst(ex["reg_std"], b).fill_(self.std[b])
             # --- what the caller reads: strided views over the instances
             hr = (oc.Cout, eng.Hout, eng.Wout)
             self.losses = self._strided(ex["loss"])
@@ -436,6 +459,56 @@ class GroupedFits:
             raise ValueError(f"GroupedFits: param_noise_seeds holds one seed per instance: got {len(sd)} for {B} nets")
         return float(weight_decay), [float(s) for s in stds], [s & 0xFFFFFFFFFFFFFFFF for s in sd]
 
+    @staticmethod
+    def _check_sweep(x, what, B, setter=False):
+        """lr / reg_noise_std as one float, or as B floats = per-instance rows of the slab; the ValueError that says what is
+        wrong otherwise.  A list of noise levels that are all zero is the float 0; a construction list that mixes zero and
+        positive levels is refused (setter: the rows exist, an instance may go to 0)."""
+        import math
+        import numbers
+        ok = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v) and v >= 0
+        seq = isinstance(x, (list, tuple)) or (hasattr(x, "__len__") and getattr(x, "ndim", 1) > 0
+                                                and not isinstance(x, (str, bytes)))
+        if not seq and not setter:
+            return float(x)                       # (one value for all: a launch argument, taken as it always was)
+        xs = list(x) if seq else [x] * B
+        if len(xs) != B:
+            raise ValueError(f"dip-amd: GroupedFits: {what} is one float or one per instance: got {len(xs)} for {B} nets")
+        if not all(ok(v) for v in xs):
+            raise ValueError(f"dip-amd: GroupedFits: {what} must hold finite numbers >= 0, got {xs!r}")
+        xs = [float(v) for v in xs]
+        if what == "reg_noise_std" and not setter:
+            if all(v == 0 for v in xs):
+                return 0.0
+            if any(v == 0 for v in xs):
+                raise ValueError(f"dip-amd: GroupedFits: reg_noise_std mixes zero and positive levels ({xs}): a solo fit at level 0 "
+                                 "feeds net_input_saved itself, an instance at 0 on the noise path would differ from it where the "
+                                 "input holds -0.0; fit the instances without noise in a group of their own (set_reg_noise_std "
+                                 "may take an instance to 0 at run time)")
+        return xs
+
+    def set_lr(self, lr):
+        """Other learning rates (B floats; one float serves all) for the iterations that follow: FusedAdam.set_lr per instance.
+        The fp64 rows are rewritten in stream order; the launch list and a captured hipGraph stay as they are."""
+        if not self._lr_rows:
+            raise ValueError("dip-amd: GroupedFits.set_lr on a group whose lr is a launch argument: construct the group with a "
+                             "list (lr=[lr] * B anneals a common value)")
+        lrs = self._check_sweep(lr, "lr", self.B, setter=True)
+        for b, v in enumerate(lrs):
+            self._inst(self._row0_extra["lr"], b).fill_(v)
+        self.lr = lrs
+
+    def set_reg_noise_std(self, std):
+        """Other input-noise levels (B floats; one float serves all) for the iterations that follow: RegNoise.set_std per
+        instance, in stream order, without a re-plan or a re-capture.  An instance may go to 0: it then gets saved + 0 * N."""
+        if not self._std_rows:
+            raise ValueError("dip-amd: GroupedFits.set_reg_noise_std on a group whose level is a launch argument: construct the "
+                             "group with a list (reg_noise_std=[std] * B anneals a common value)")
+        stds = self._check_sweep(std, "reg_noise_std", self.B, setter=True)
+        for b, v in enumerate(stds):
+            self._inst(self._row0_extra["reg_std"], b).fill_(v)
+        self.std = stds
+
     def _sgld_state(self, b):
         """Instance b's DipSgldState {offset 0, seed, std} as int64[3] on the host."""
         s = N.DipSgldState(0, self.param_noise_seeds[b], self.param_noise_std[b], 0.0)
@@ -561,7 +634,7 @@ class GroupedFits:
         nin, nout = Cimg * H * W, Cn * Hn * Wn
         ex = {}
         ex["saved"] = slab.alloc(nin)                       # net_input_saved (denoising.ipynb:198)
-        ex["noisy"] = slab.alloc(nin) if self.std > 0 else None
+        ex["noisy"] = slab.alloc(nin) if self._noisy else None
         ex["rng"] = slab.alloc(2, torch.int64, zero=True)   # {Philox offset, seed} (dip_noise_axpy_dev2)
         if sr:
             ex["taps"] = slab.alloc(k * k)                  # per-instance data: every pointer of a grouped launch is in the slab
@@ -588,7 +661,7 @@ class GroupedFits:
         ex["v"] = slab.alloc(eng.n_arena, zero=True)
         ex["iter"] = slab.alloc(16, torch.uint8, zero=True)  # DipIterState: step count, step size, sqrt(bias correction 2)
         self._row0_extra = ex
-        self._x = ex["noisy"] if self.std > 0 else ex["saved"]
+        self._x = ex["noisy"] if self._noisy else ex["saved"]
         at = lambda k: None if ex[k] is None else ex[k].data_ptr()
         if sr:
             self._head = LH.sr_descriptor(eng, geom, at("out"), at("taps"), at("target"), at("y"), at("partials"), self.nblk,
@@ -624,6 +697,13 @@ class GroupedFits:
             if self._sgld_ranges:
                 ex["sgld_ranges"][:2 * len(self._sgld_ranges)].copy_(
                     torch.tensor(self._sgld_ranges, dtype=torch.int64).reshape(-1))
+        # a sweep's scalars, only when the keyword is a list and behind everything else: no other row's offset moves
+        if self._lr_rows:
+            ex["lr"] = slab.alloc(1, torch.float64)             # dip_adam_tick_dev reads it
+            ex["lr"].fill_(self.lr[0])
+        if self._std_rows:
+            ex["reg_std"] = slab.alloc(1)                       # dip_noise_axpy_dev3 reads it
+            ex["reg_std"].fill_(self.std[0])
 
     def _monitor_sizes(self, m):
         from utils.fit_monitor import monitor_sizes
@@ -718,7 +798,10 @@ class GroupedFits:
         N.check(lib.dip_group_begin(self.B, self.stride, self.mem.data_ptr(), self.stride), "group_begin")
         try:
             # closure: net_input = net_input_saved + noise.normal_() * reg_noise_std
-            if self.std > 0:
+            if self._std_rows:              # a sweep: every instance reads the level of its own row
+                N.check(lib.dip_noise_axpy_dev3(ex["saved"].data_ptr(), ex["noisy"].data_ptr(), ex["saved"].numel(),
+                                                ex["reg_std"].data_ptr(), ex["rng"].data_ptr(), st), "noise_axpy_dev3")
+            elif self._noisy:
                 N.check(lib.dip_noise_axpy_dev2(ex["saved"].data_ptr(), ex["noisy"].data_ptr(), ex["saved"].numel(), self.std,
                                                 ex["rng"].data_ptr(), st), "noise_axpy_dev2")
             # out = net(net_input); total_loss = mse(out [* mask], target [* mask])
@@ -740,7 +823,12 @@ class GroupedFits:
                 for fn, args, name in getattr(self, ops):
                     N.check(fn(*args, st), name)
             # optimizer.step(): torch.optim.Adam semantics (dip_optim.FusedAdam), step count on the device
-            N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st), "adam_tick")
+            if self._lr_rows:
+                N.check(lib.dip_adam_tick_dev(ex["iter"].data_ptr(), ex["lr"].data_ptr(), self.ADAM_BETAS[0], self.ADAM_BETAS[1],
+                                              st), "adam_tick_dev")
+            else:
+                N.check(lib.dip_adam_tick(ex["iter"].data_ptr(), self.lr, self.ADAM_BETAS[0], self.ADAM_BETAS[1], st),
+                        "adam_tick")
             if self.sgld:                   # FusedAdam(weight_decay=, noise_std=, noise_seed=) per instance, ONE launch
                 N.check(lib.dip_adam_sgld_step_dev(eng.params.data_ptr(), eng.grads.data_ptr(), ex["m"].data_ptr(),
                                                    ex["v"].data_ptr(), self._sgld_n, self.ADAM_BETAS[0], self.ADAM_BETAS[1],

@@ -292,6 +292,9 @@ _SIGS = {
                                     C.c_double, C.c_void_p, C.c_void_p]),
     "dip_noise_axpy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p]),
     "dip_noise_axpy_dev2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "dip_adam_tick_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    "dip_noise_axpy_dev3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dip_noise_axpy_dev1s": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "dip_counter_add": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "dip_counter_add_n": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
     "dip_group_begin": (C.c_int, [C.c_int, C.c_longlong, C.c_void_p, C.c_longlong]),

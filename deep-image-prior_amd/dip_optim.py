@@ -92,12 +92,20 @@ class FusedAdam:
 
     With weight_decay == 0 and noise_std == 0 at construction the optimiser issues what it always issued (dip_adam_tick +
     dip_adam_step_dev); otherwise dip_adam_tick + dip_adam_sgld_step_dev, also after set_noise_std(0): the stream keeps
-    advancing.  Everything that varies per step is in device memory, so GraphedIteration captures the step as it is."""
+    advancing.  Everything that varies per step is in device memory, so GraphedIteration captures the step as it is.
+
+    device_lr=True: lr, too, lives in device memory -- one fp64 scalar per device next to the DipIterState -- and the tick reads it
+    there (dip_adam_tick_dev, the arithmetic of dip_adam_tick).  set_lr(x) rewrites it in stream order: a learning-rate schedule
+    under a captured GraphedIteration, and no re-plan of a NativeIteration.  `lr` is the host mirror."""
 
     def __init__(self, parameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, noise_std=0.0, noise_seed=0,
-                 noise_params=None):
+                 noise_params=None, device_lr=False):
         self.params = [p for p in parameters]
+        self.device_lr = bool(device_lr)
+        if self.device_lr:
+            lr = self._check_lr(lr, "FusedAdam")
         self.lr, self.betas, self.eps = lr, betas, eps
+        self._lr_dev = {}                      # device -> the fp64 scalar dip_adam_tick_dev reads (device_lr only)
         if not float(weight_decay) >= 0.0:                          # (a NaN compares false)
             raise ValueError(f"dip-amd: FusedAdam: weight_decay must be >= 0, got {weight_decay}")
         if not float(noise_std) >= 0.0:
@@ -116,6 +124,38 @@ class FusedAdam:
         self._groups = None
         self._sig = None
         self._iter_state = {}                  # device -> DipIterState bytes (uint8[16])
+
+    @staticmethod
+    def _check_lr(lr, who):
+        import math
+        import numbers
+        if isinstance(lr, bool) or not isinstance(lr, numbers.Real) or not math.isfinite(lr) or lr < 0:
+            raise ValueError(f"dip-amd: {who}: lr must be a finite number >= 0, got {lr!r}")
+        return float(lr)
+
+    def set_lr(self, lr):
+        """The learning rate from the next step on: one 8-byte fill per device on the current stream, no synchronisation.
+        Neither a NativeIteration plan nor a captured GraphedIteration holds the value."""
+        if not self.device_lr:
+            raise RuntimeError("dip-amd: FusedAdam.set_lr: this optimiser passes lr as a launch argument (a plan or a captured "
+                               "graph would keep the old value); construct it with device_lr=True")
+        self.lr = self._check_lr(lr, "FusedAdam.set_lr")
+        for t in self._lr_dev.values():
+            t.fill_(self.lr)
+
+    def _lr_scalar(self, dev):
+        """The fp64 lr scalar of device `dev` (device_lr only), created holding the host mirror."""
+        t = self._lr_dev.get(dev)
+        if t is None:
+            t = self._lr_dev[dev] = torch.full((1,), float(self.lr), dtype=torch.float64, device=dev)
+        return t
+
+    def _tick_launch(self, lib, dev, st):
+        """(fn, args without the stream, name) of the tick: what step() issues and NativeIteration's Adam phase starts with."""
+        b1, b2 = float(self.betas[0]), float(self.betas[1])
+        if self.device_lr:
+            return lib.dip_adam_tick_dev, (st.data_ptr(), self._lr_scalar(dev).data_ptr(), b1, b2), "adam_tick_dev"
+        return lib.dip_adam_tick, (st.data_ptr(), float(self.lr), b1, b2), "adam_tick"
 
     def set_noise_std(self, std):
         """The noise level from the next step on: written into every group's DipSgldState on the current stream.  No re-plan
@@ -228,8 +268,8 @@ class FusedAdam:
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 st = self._state(dev, self.step_count - 1)
                 if dev not in ticked:          # t <- t + 1, step_size and sqrt(bc2) in double, on the device
-                    N.check(lib.dip_adam_tick(st.data_ptr(), float(self.lr), float(self.betas[0]),
-                                              float(self.betas[1]), stream), "adam_tick")
+                    fn, args, name = self._tick_launch(lib, dev, st)
+                    N.check(fn(*args, stream), name)
                     ticked.add(dev)
                 fn, args, name = self._step_launch(lib, g, flat_ptr, st)
                 N.check(fn(*args, stream), name)
@@ -247,8 +287,9 @@ class FusedAdam:
                 "adam_sgld_step_dev")
 
     def _plan_key(self):
-        """What NativeIteration's Adam phase was built from; with the defaults, what it always was."""
-        key = (self.lr, self.betas, self.eps, id(self._groups))
+        """What NativeIteration's Adam phase was built from; with the defaults, what it always was.  device_lr: the identity of
+        the table of lr scalars stands where the value of lr stands (set_lr changes neither the table nor its tensors)."""
+        key = (("lr_dev", id(self._lr_dev)) if self.device_lr else self.lr, self.betas, self.eps, id(self._groups))
         if self.sgld:
             key += (self.weight_decay, tuple((id(g.sgld), id(g.range_table), tuple(g.ranges)) for g in self._groups or ()))
         return key
@@ -278,7 +319,8 @@ class GraphedIteration:
 
     The closure must be replay-safe: no host synchronisation (.item(), .cpu(), print of a tensor),
     every tensor it keeps across iterations updated IN PLACE, reg-noise from utils.reg_noise.RegNoise
-    (or torch's graph-safe device generator).  `lr` is frozen at capture time.
+    (or torch's graph-safe device generator).  `lr` is frozen at capture time unless `device_lr=True`
+    (FusedAdam(..., device_lr=True): opt.set_lr(x) between run() calls; RegNoise(..., device_std=True) likewise).
 
         it = GraphedIteration(optimizer, closure)     # 3 eager warm-up iterations, then the capture
         it.run(num_iter - 3)
@@ -610,7 +652,7 @@ class NativeIteration:
         return (id(eng._clists), eng.shape_key, id(getattr(eng, "fwd_ops", None)), id(getattr(eng, "bwd_ops", None)), sig,
                 *opt._plan_key(),
                 head._plan_key(),
-                None if reg is None else (reg.std, reg.seed, id(reg.saved), id(reg.out), id(reg.offset))) \
+                None if reg is None else reg._plan_key()) \
             + tuple((slot, m._plan_key()) for slot, m in self._monitors())       # (no monitors: the key as it was)
 
     def _build(self):
@@ -618,7 +660,7 @@ class NativeIteration:
         lib = N.lib()
         dev = self.device
         self._check_monitors()
-        noisy = reg is not None and reg.std > 0
+        noisy = reg is not None and reg.noisy
         x = self.net_input if reg is None else (reg.out if noisy else reg.saved)
         _, Cimg, H, W = x.shape
         eng._prepare(dev, H, W, Cimg)
@@ -632,16 +674,14 @@ class NativeIteration:
         desc = head._descriptor(eng, out, loss0)
         pre = []
         if noisy:
-            pre.append((lib.dip_noise_axpy_dev, (reg.saved.data_ptr(), reg.out.data_ptr(), reg.saved.numel(), reg.std,
-                                                 reg.seed, reg.offset.data_ptr()), "noise_axpy_dev"))
+            pre.append(reg._launch(lib))           # dip_noise_axpy_dev, or dip_noise_axpy_dev1s on the device-side level
         pre += eng._forward_prologue(x.data_ptr())
         mid = head.fwd_launches(eng, desc)
         if len(eng.bns):
             mid.append((lib.dip_counter_add_n, (eng.nbt.data_ptr(), eng.nbt.numel(), 1), "num_batches_tracked"))
         mid += head.bwd_launches(eng, desc, self._one.data_ptr())
         st = opt._state(dev, opt.step_count)
-        b1, b2 = float(opt.betas[0]), float(opt.betas[1])
-        adam = [(lib.dip_adam_tick, (st.data_ptr(), float(opt.lr), b1, b2), "adam_tick")]
+        adam = [opt._tick_launch(lib, dev, st)]    # dip_adam_tick, or dip_adam_tick_dev on the device-side lr
         pbase, gbase = eng.params.data_ptr(), eng.grads.data_ptr()
         for g in opt._groups:
             if g.params[0].device != dev or g.base < pbase or g.base + 4 * g.numel > pbase + 4 * eng.params.numel():
@@ -670,7 +710,8 @@ class NativeIteration:
                           loss0=loss0,
                           keep=(head._plan_keep(), eng._clists, eng.fwd_ops, eng.bwd_ops, opt._groups,
                                 eng.params, eng.grads, eng.nbt, eng.dy_out,
-                                None if reg is None else (reg.saved, reg.out, reg.offset),
+                                None if reg is None else (reg.saved, reg.out, reg.offset, reg.std_dev),
+                                opt._lr_dev.get(dev),
                                 [m._plan_keep() for _, m in self._monitors()]))
         self._key = self._signature(opt._sig)
 

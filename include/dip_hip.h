@@ -575,6 +575,24 @@ int dip_noise_axpy_dev(const float* z, float* out, int64_t n, float sigma, uint6
 /* dip_noise_axpy_dev with the seed in device memory too: state_dev = {offset, seed} (two uint64).  In a group every
  * instance reads its own pair, i.e. draws its own stream. */
 int dip_noise_axpy_dev2(const float* z, float* out, int64_t n, float sigma, uint64_t* state_dev, void* stream);
+/* The hyper-parameters of a sweep or a schedule in DEVICE memory, next to the state above: the launch reads the scalar where it
+ * lives, a setter rewrites it in stream order (one fill on the stream), and neither a command array nor a captured hipGraph
+ * holds its value.  Inside dip_group_begin / dip_group_end lr_dev / sigma_dev are grouped pointers like st / state_dev: every
+ * instance reads the scalar of its own slab row.
+ *
+ * dip_adam_tick_dev: dip_adam_tick with lr = *lr_dev (one fp64).  The same double arithmetic in the same order:
+ *     t <- t + 1;  step_size = (float)(lr / (1 - beta1^t));  bc2_sqrt = (float)sqrt(1 - beta2^t)
+ * so the 16 bytes of *st are those dip_adam_tick writes for the same lr.
+ * dip_noise_axpy_dev3: dip_noise_axpy_dev2 with sigma = *sigma_dev (one fp32): out[i] = fmaf(sigma, N_i, z[i]), N_i normal
+ * i % 4 of Philox quad offset + i / 4 under key seed, {offset, seed} = state_dev[0..1]; state_dev[0] += ceil(n / 4) behind the
+ * launch.  sigma == 0 still draws and advances: out = z + 0 * N (a -0.0 of z comes out as +0.0).
+ * dip_noise_axpy_dev1s: the solo counterpart, dip_noise_axpy_dev with sigma = *sigma_dev: the seed by value, the offset at
+ * *offset_dev, advanced the same way.  All three run the body of the kernel they are named after.
+ * A NULL st / lr_dev / z / out / sigma_dev / state_dev / offset_dev, or n <= 0, returns -1 before anything is launched. */
+int dip_adam_tick_dev(DipIterState* st, const double* lr_dev, double beta1, double beta2, void* stream);
+int dip_noise_axpy_dev3(const float* z, float* out, int64_t n, const float* sigma_dev, uint64_t* state_dev, void* stream);
+int dip_noise_axpy_dev1s(const float* z, float* out, int64_t n, const float* sigma_dev, uint64_t seed, uint64_t* offset_dev,
+                         void* stream);
 /* *counter += inc (one thread; ordering by the stream). */
 int dip_counter_add(uint64_t* counter, uint64_t inc, void* stream);
 /* counters[i] += inc for i < n in one launch: `num_batches_tracked += 1` of every nn.BatchNorm2d of the net in train mode
