@@ -53,6 +53,7 @@ const Entry g_fns[] = {
     DIP_REG(dip_adam_step), DIP_REG(dip_noise_axpy), DIP_REG(dip_adam_tick), DIP_REG(dip_adam_step_dev),
     DIP_REG(dip_noise_axpy_dev), DIP_REG(dip_noise_axpy_dev2), DIP_REG(dip_counter_add), DIP_REG(dip_counter_add_n),
     DIP_REG(dip_adam_sgld_step), DIP_REG(dip_adam_sgld_step_dev), DIP_REG(dip_posterior_dev),
+    DIP_REG(dip_posterior_rec_dev), DIP_REG(dip_posterior_pool),
     DIP_REG(dip_adam_tick_dev), DIP_REG(dip_noise_axpy_dev3), DIP_REG(dip_noise_axpy_dev1s),
     DIP_REG(dip_loss_head_fwd), DIP_REG(dip_loss_head_bwd), DIP_REG(dip_sr_loss_fwd), DIP_REG(dip_sr_loss_bwd),
     DIP_REG(dip_sr_tv_loss_fwd), DIP_REG(dip_sr_tv_loss_bwd),

@@ -157,29 +157,68 @@ __device__ __forceinline__ bool posterior_is_sample(int it, int count, int burn_
     return it >= burn_in && (it - burn_in) % every == 0 && count >= 0 && count < DIP_POSTERIOR_MAX_SAMPLES;
 }
 
-template <bool GRP = false>
-__global__ __launch_bounds__(256) void posterior_update_kernel(const float* __restrict__ out_, float* __restrict__ mean_,
-                                                               float* __restrict__ m2_, int64_t n, int burn_in, int every,
-                                                               const int* __restrict__ counter_, const int* __restrict__ count_,
-                                                               const DipGrpArg<GRP> grp) {
+// REC (dip_posterior_rec_dev): the same pass also leaves the block's fp64 sum of (double(mean') - double(gt))^2 over the
+// just-updated mean in partial[blockIdx.x]; mean and m2 come from the very statements of REC = false.
+template <bool REC>
+__device__ __forceinline__ void posterior_update_body(const float* __restrict__ out, float* __restrict__ mean,
+                                                      float* __restrict__ m2, int64_t n, int burn_in, int every,
+                                                      const int* __restrict__ counter, const int* __restrict__ count,
+                                                      const float* __restrict__ gt, double* __restrict__ partial) {
     // Every operation rounds on its own: without the pragma m2 + d * (x - mean') becomes one FMA.  It is lexical, and
     // __fmul_rn / __fadd_rn are plain * and + in a header, outside its reach: the operators themselves are written here.
 #pragma clang fp contract(off)
-    DIP_GRP_PTR(const float*, out);
-    DIP_GRP_PTR(float*, mean);
-    DIP_GRP_PTR(float*, m2);
-    DIP_GRP_PTR(const int*, counter);
-    DIP_GRP_PTR(const int*, count);
     const int it = counter[0], cnt = count[0];    // uniform
     if (it < 0 || !posterior_is_sample(it, cnt, burn_in, every)) return;
     const float k = (float)(cnt + 1);
+    double s = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float x = out[i], mu = mean[i];
         const float d = x - mu;
         const float mu2 = mu + __fdiv_rn(d, k);
         mean[i] = mu2;
         m2[i] = m2[i] + d * (x - mu2);
+        if constexpr (REC) {
+            const double e = (double)mu2 - (double)gt[i];
+            s = s + e * e;
+        }
     }
+    if constexpr (REC) mon_block_sum<double>(s, partial + blockIdx.x);
+}
+
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void posterior_update_kernel(const float* __restrict__ out_, float* __restrict__ mean_,
+                                                               float* __restrict__ m2_, int64_t n, int burn_in, int every,
+                                                               const int* __restrict__ counter_, const int* __restrict__ count_,
+                                                               const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float*, out);
+    DIP_GRP_PTR(float*, mean);
+    DIP_GRP_PTR(float*, m2);
+    DIP_GRP_PTR(const int*, counter);
+    DIP_GRP_PTR(const int*, count);
+    posterior_update_body<false>(out, mean, m2, n, burn_in, every, counter, count, nullptr, nullptr);
+}
+
+template <bool GRP = false>
+__global__ __launch_bounds__(256) void posterior_update_rec_kernel(const float* __restrict__ out_, float* __restrict__ mean_,
+                                                                   float* __restrict__ m2_, int64_t n, int burn_in, int every,
+                                                                   const int* __restrict__ counter_,
+                                                                   const int* __restrict__ count_, const float* __restrict__ gt_,
+                                                                   double* __restrict__ partial_, const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(const float*, out);
+    DIP_GRP_PTR(float*, mean);
+    DIP_GRP_PTR(float*, m2);
+    DIP_GRP_PTR(const int*, counter);
+    DIP_GRP_PTR(const int*, count);
+    DIP_GRP_PTR(const float*, gt);
+    DIP_GRP_PTR(double*, partial);
+    posterior_update_body<true>(out, mean, m2, n, burn_in, every, counter, count, gt, partial);
+}
+
+__device__ __forceinline__ void posterior_advance(int burn_in, int every, int* __restrict__ counter, int* __restrict__ count) {
+    const int it = counter[0], cnt = count[0];
+    if (it < 0 || it == 0x7fffffff) return;       // (a counter the host did not initialise)
+    if (posterior_is_sample(it, cnt, burn_in, every)) count[0] = cnt + 1;
+    counter[0] = it + 1;
 }
 
 template <bool GRP = false>
@@ -188,10 +227,150 @@ __global__ __launch_bounds__(64) void posterior_advance_kernel(int burn_in, int 
     DIP_GRP_PTR(int*, counter);
     DIP_GRP_PTR(int*, count);
     if (threadIdx.x != 0) return;
+    posterior_advance(burn_in, every, counter, count);
+}
+
+// The one-thread kernel of dip_posterior_rec_dev: on a sample iteration it adds the nblk fp64 partials in block order and writes
+// row `count` of records -- {iteration, mse_mean, psnr_mean} -- before count and counter advance as above.  A row outside
+// [0, capacity) is not written (the host refuses first); the sample itself has been taken.
+template <bool GRP = false>
+__global__ __launch_bounds__(64) void posterior_record_kernel(int burn_in, int every, int* __restrict__ counter_,
+                                                              int* __restrict__ count_, const double* __restrict__ partial_,
+                                                              int nblk, int64_t n, float* __restrict__ records_, int capacity,
+                                                              const DipGrpArg<GRP> grp) {
+    DIP_GRP_PTR(int*, counter);
+    DIP_GRP_PTR(int*, count);
+    DIP_GRP_PTR(const double*, partial);
+    DIP_GRP_PTR(float*, records);
+    if (threadIdx.x != 0) return;
     const int it = counter[0], cnt = count[0];
-    if (it < 0 || it == 0x7fffffff) return;       // (a counter the host did not initialise)
-    if (posterior_is_sample(it, cnt, burn_in, every)) count[0] = cnt + 1;
-    counter[0] = it + 1;
+    if (it >= 0 && it != 0x7fffffff && posterior_is_sample(it, cnt, burn_in, every) && mon_in_range(cnt, capacity)) {
+        double s = 0.0;
+        for (int b = 0; b < nblk; ++b) s += partial[b];
+        float* row = records + 3 * (int64_t)cnt;
+        row[0] = (float)it;
+        row[1] = (float)(s / (double)n);
+        row[2] = mon_psnr(s, n);
+    }
+    posterior_advance(burn_in, every, counter, count);
+}
+
+// ---------------------------------------------------------------- pooling the chains of a grouped posterior (Gelman-Rubin)
+// Row c of `mean` / `m2` lies chains[c] * stride bytes behind row 0.  Per element, L lanes at a time (L = 4: 16-byte accesses),
+// in individually rounded fp32 operations, walking the chains in list order (include/dip_hip.h states the arithmetic).
+template <int L> struct PoolVec { using T = float; };
+template <> struct PoolVec<4> { using T = f32x4; };
+
+template <int L>
+__device__ __forceinline__ void pool_elements(const char* __restrict__ mean0, const char* __restrict__ m20, long long stride,
+                                              const int* __restrict__ chains, int nchains, int64_t i, float fc, float fck,
+                                              float fc1, float f, float* __restrict__ mean, float* __restrict__ var,
+                                              float* __restrict__ within, float* __restrict__ rhat, double& rsum, double& rmax,
+                                              double& ndeg) {
+#pragma clang fp contract(off)
+    using V = typename PoolVec<L>::T;
+    union U { V v; float f[L]; };
+    float s[L], w[L], q[L], mu[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) s[j] = w[j] = q[j] = 0.f;
+    for (int c = 0; c < nchains; ++c) {
+        const long long off = (long long)chains[c] * stride;
+        U a, b;
+        a.v = *reinterpret_cast<const V*>(mean0 + off + 4 * i);
+        b.v = *reinterpret_cast<const V*>(m20 + off + 4 * i);
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            s[j] = s[j] + a.f[j];
+            w[j] = w[j] + b.f[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < L; ++j) mu[j] = __fdiv_rn(s[j], fc);
+    for (int c = 0; c < nchains; ++c) {
+        U a;
+        a.v = *reinterpret_cast<const V*>(mean0 + (long long)chains[c] * stride + 4 * i);
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            const float d = a.f[j] - mu[j];
+            q[j] = q[j] + d * d;
+        }
+    }
+    U om, ov, ow, orh;
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        const float W = __fdiv_rn(w[j], fck);
+        const float Bk = __fdiv_rn(q[j], fc1);
+        const float Vv = f * W + Bk;
+        float R;
+        if (W > 0.f) {
+            R = sqrtf(__fdiv_rn(Vv, W));          // (correctly rounded; __fsqrt_rn is the native, 1-ulp square root here)
+            rsum += (double)R;
+            rmax = fmax(rmax, (double)R);
+        } else {                                  // degenerate (no within-chain variance, or a NaN): left out of the summary
+            R = __builtin_nanf("");
+            ndeg += 1.0;
+        }
+        om.f[j] = mu[j]; ov.f[j] = Vv; ow.f[j] = W; orh.f[j] = R;
+    }
+    *reinterpret_cast<V*>(mean + i) = om.v;
+    *reinterpret_cast<V*>(var + i) = ov.v;
+    *reinterpret_cast<V*>(within + i) = ow.v;
+    if (rhat != nullptr) *reinterpret_cast<V*>(rhat + i) = orh.v;
+}
+
+// VEC: every row and every output is 16-byte aligned -- quads, then the n % 4 elements behind them one by one.
+// partial[3 * blockIdx.x + {0, 1, 2}] = the block's {sum of R, max of R, number of degenerate elements} in fp64.
+template <bool VEC>
+__global__ __launch_bounds__(256) void posterior_pool_kernel(const char* __restrict__ mean0, const char* __restrict__ m20,
+                                                             long long stride, const int* __restrict__ chains, int nchains,
+                                                             int64_t n, float fc, float fck, float fc1, float f,
+                                                             float* __restrict__ mean, float* __restrict__ var,
+                                                             float* __restrict__ within, float* __restrict__ rhat,
+                                                             double* __restrict__ partial) {
+    __shared__ double sh[3][256];
+    double rsum = 0.0, rmax = -1.0, ndeg = 0.0;   // (R >= 0: -1 says "no element yet")
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if constexpr (VEC) {
+        const int64_t nq = n / 4;
+        for (int64_t qd = t; qd < nq; qd += step)
+            pool_elements<4>(mean0, m20, stride, chains, nchains, 4 * qd, fc, fck, fc1, f, mean, var, within, rhat, rsum, rmax,
+                             ndeg);
+        for (int64_t i = 4 * nq + t; i < n; i += step)
+            pool_elements<1>(mean0, m20, stride, chains, nchains, i, fc, fck, fc1, f, mean, var, within, rhat, rsum, rmax, ndeg);
+    } else {
+        for (int64_t i = t; i < n; i += step)
+            pool_elements<1>(mean0, m20, stride, chains, nchains, i, fc, fck, fc1, f, mean, var, within, rhat, rsum, rmax, ndeg);
+    }
+    sh[0][threadIdx.x] = rsum; sh[1][threadIdx.x] = rmax; sh[2][threadIdx.x] = ndeg;
+    for (int s = 128; s >= 1; s >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < s) {
+            sh[0][threadIdx.x] += sh[0][threadIdx.x + s];
+            sh[1][threadIdx.x] = fmax(sh[1][threadIdx.x], sh[1][threadIdx.x + s]);
+            sh[2][threadIdx.x] += sh[2][threadIdx.x + s];
+        }
+    }
+    if (threadIdx.x == 0) {
+        partial[3 * blockIdx.x + 0] = sh[0][0];
+        partial[3 * blockIdx.x + 1] = sh[1][0];
+        partial[3 * blockIdx.x + 2] = sh[2][0];
+    }
+}
+
+// summary = {mean of R over the non-degenerate elements, their max, the number of degenerate ones}; NaN, NaN, n when all are.
+__global__ __launch_bounds__(64) void posterior_pool_finalize_kernel(const double* __restrict__ partial, int nblk, int64_t n,
+                                                                     double* __restrict__ summary) {
+    if (threadIdx.x != 0) return;
+    double rsum = 0.0, rmax = -1.0, ndeg = 0.0;
+    for (int b = 0; b < nblk; ++b) {
+        rsum += partial[3 * b + 0];
+        rmax = fmax(rmax, partial[3 * b + 1]);
+        ndeg += partial[3 * b + 2];
+    }
+    const double good = (double)n - ndeg;
+    summary[0] = good > 0.0 ? rsum / good : __builtin_nan("");
+    summary[1] = good > 0.0 ? rmax : __builtin_nan("");
+    summary[2] = ndeg;
 }
 
 }  // namespace
@@ -210,6 +389,59 @@ extern "C" int dip_posterior_dev(const DipPosteriorDesc* d, void* stream) {
     DIP_CHECK_LAUNCH();
     dip_launch_pair<DIP_FAM_LOSS>(posterior_advance_kernel<false>, posterior_advance_kernel<true>, dim3(1), dim3(64), 0, st,
                                   d->burn_in, d->every, d->counter, d->count);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_posterior_rec_dev(const DipPosteriorRecDesc* d, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d == nullptr) DIP_FAIL("posterior_rec_dev: NULL descriptor");
+    if (d->out == nullptr || d->mean == nullptr || d->m2 == nullptr || d->count == nullptr || d->counter == nullptr ||
+        d->gt == nullptr || d->partial == nullptr || d->records == nullptr)
+        DIP_FAIL("posterior_rec_dev: a required pointer is NULL");
+    if (d->n <= 0 || d->burn_in < 0 || d->every < 1 || d->capacity < 1)
+        DIP_FAIL("posterior_rec_dev: n > 0, burn_in >= 0, every >= 1 and capacity >= 1 are required");
+    if (d->n > ((int64_t)1 << 33)) DIP_FAIL("posterior_rec_dev: n must be <= 2^33");
+    const int nblk = dip_fit_monitor_nblk(d->n);
+    dip_launch_pair<DIP_FAM_LOSS>(posterior_update_rec_kernel<false>, posterior_update_rec_kernel<true>, dim3(nblk), dim3(256), 0,
+                                  st, d->out, d->mean, d->m2, d->n, d->burn_in, d->every, (const int*)d->counter,
+                                  (const int*)d->count, d->gt, d->partial);
+    DIP_CHECK_LAUNCH();
+    dip_launch_pair<DIP_FAM_LOSS>(posterior_record_kernel<false>, posterior_record_kernel<true>, dim3(1), dim3(64), 0, st,
+                                  d->burn_in, d->every, d->counter, d->count, (const double*)d->partial, nblk, d->n, d->records,
+                                  d->capacity);
+    DIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dip_posterior_pool(const float* mean0, const float* m20, long long stride, const int* chains, int nchains, int k,
+                                  int64_t n, float* mean, float* var, float* within, float* rhat, double* partial,
+                                  double* summary, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dip_group_ctx()->ninst > 1) DIP_FAIL("posterior_pool: a group bracket is open (the launch pools rows, it is not one of them)");
+    if (mean0 == nullptr || m20 == nullptr || chains == nullptr || mean == nullptr || var == nullptr || within == nullptr ||
+        partial == nullptr || summary == nullptr)
+        DIP_FAIL("posterior_pool: a required pointer is NULL");
+    if (n <= 0 || n > ((int64_t)1 << 33)) DIP_FAIL("posterior_pool: n must be in (0, 2^33]");
+    if (k < 2 || k > DIP_POSTERIOR_MAX_SAMPLES) DIP_FAIL("posterior_pool: k (samples per chain) must be in [2, 2^24]");
+    if (nchains < 2 || nchains > (1 << 16)) DIP_FAIL("posterior_pool: at least 2 chains (and at most 65536) are pooled");
+    uintptr_t bits = reinterpret_cast<uintptr_t>(mean0) | reinterpret_cast<uintptr_t>(m20) | (uintptr_t)stride |
+                     reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(var) |
+                     reinterpret_cast<uintptr_t>(within) | reinterpret_cast<uintptr_t>(rhat);
+    if (bits & 3) DIP_FAIL("posterior_pool: rows, stride and outputs must be 4-byte aligned");
+    const float fc = (float)nchains, fck = (float)((int64_t)nchains * (k - 1)), fc1 = (float)(nchains - 1);
+    const float f = (float)(k - 1) / (float)k;
+    const int nblk = dip_fit_monitor_nblk(n);
+    const char* a = reinterpret_cast<const char*>(mean0);
+    const char* b = reinterpret_cast<const char*>(m20);
+    if (bits & 15)
+        posterior_pool_kernel<false><<<dim3(nblk), dim3(256), 0, st>>>(a, b, stride, chains, nchains, n, fc, fck, fc1, f, mean, var,
+                                                                      within, rhat, partial);
+    else
+        posterior_pool_kernel<true><<<dim3(nblk), dim3(256), 0, st>>>(a, b, stride, chains, nchains, n, fc, fck, fc1, f, mean, var,
+                                                                     within, rhat, partial);
+    DIP_CHECK_LAUNCH();
+    posterior_pool_finalize_kernel<<<dim3(1), dim3(64), 0, st>>>((const double*)partial, nblk, n, summary);
     DIP_CHECK_LAUNCH();
     return 0;
 }

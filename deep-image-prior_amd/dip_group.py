@@ -116,6 +116,26 @@ instance is bit-identical to its solo NativeIteration fit with the same seeds (t
 
     g = GroupedFits(nets, net_inputs, imgs_noisy, reg_noise_std=1/30, weight_decay=5e-8, param_noise_std=[1e-4, 2e-4, 4e-4])
 
+The posterior of such fits, per instance and pooled: `posterior=utils.fit_monitor.GroupedPosteriorMonitor(burn_in, every=1,
+imgs_gt=None)`, a fourth keyword for all three group kinds (a super-resolution group samples the HR output).  Its rows -- mean,
+m2, the sample count and the iteration counter; with imgs_gt also the ground truth, fp64 partials and a [capacity, 3] record
+table of the posterior mean's PSNR, one row per sample -- are per-instance data of the slab behind everything else a row owns,
+the sgld and the lr / reg_std rows included, and only when the keyword is set.  ONE dip_posterior_dev (imgs_gt:
+dip_posterior_rec_dev) call inside the group bracket, behind the early_stop= launches and in front of ssim= and Adam -- the order
+of a solo NativeIteration -- serves all B inside the ONE hipGraph of capture(), and instance b's rows are those of the solo
+NativeIteration(posterior=PosteriorMonitor(...)) fit, bit for bit (tests/test_group_posterior_gpu.py).  B instances over one
+image with different param_noise_seeds are B independent chains: pm.pooled(chains=None) is ONE dip_posterior_pool launch outside
+the bracket over the rows -- the pooled mean, the within-chain variance W, the Gelman-Rubin estimate V and R-hat = sqrt(V / W)
+per element, and {mean, max, degenerate count} of R-hat as three doubles -- with nothing going through the host.
+
+    pm = GroupedPosteriorMonitor(burn_in=7000, every=50, imgs_gt=[img] * B)
+    g = GroupedFits(nets, [z] * B, [img_noisy] * B, reg_noise_std=1/30, weight_decay=5e-8, param_noise_std=1e-4,
+                    param_noise_seeds=[1, 2, 3], posterior=pm)
+    g.capture(); g.run(num_iter - 3)
+    pm.mean, pm.variance(), pm.count            # [B, C, H, W] each; the host's sample count, no synchronisation
+    pm.history()                                # [B, count, 3]: iteration, mse_mean, psnr_mean
+    p = pm.pooled(); p.mean, p.var, p.rhat, p.summary           # [1, C, H, W] each; fp64 [3]
+
 Learning-rate and input-noise sweeps: `lr=[B floats]` and / or `reg_noise_std=[B floats]` (a float is the group above, launch
 for launch and byte for byte of slab).  A list puts the values into the slab -- one fp64 row `lr`, one fp32 row `reg_std`, behind
 everything else the group owns, so no other row moves -- and ONE grouped dip_adam_tick_dev / dip_noise_axpy_dev3 stands where
@@ -178,7 +198,7 @@ class GroupedFits:
 
     def __init__(self, nets, net_inputs, targets, masks=None, reg_noise_std=0.0, seeds=None, lr=0.01, exp_weight=None,
                  ema_init="first", device=None, _dry_cpu=False, downsamplers=None, monitor=None, tv_weights=None, tv_beta=0.5,
-                 early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None, ssim=None):
+                 early_stop=None, weight_decay=0.0, param_noise_std=0.0, param_noise_seeds=None, ssim=None, posterior=None):
         """nets: B nets of models.skip.skip() with identical architecture; net_inputs / targets (/ masks): one tensor per
         instance, identical shapes ([1,C,H,W]; masks [1,1|Cout,H,W] or None).  reg_noise_std / seeds: the closure's input
         noise (utils.reg_noise.RegNoise; seeds default to 0..B-1).  lr / reg_noise_std: one float, or B floats = a sweep: the
@@ -206,13 +226,18 @@ class GroupedFits:
         two rows join the slab behind everything else: the DipSgldState and the range table of the 4-D parameters.
         ssim: None, or a utils.fit_monitor.GroupedSSIMMonitor: the mean structural similarity of every instance's output against
         its ground truth (with_avg: of the GroupedFitMonitor's smoothed output too), inside the launch list behind the
-        early_stop= launches and in front of Adam; independent of the group kind.  Its rows join the slab behind the es_ rows."""
+        early_stop= launches and in front of Adam; independent of the group kind.  Its rows join the slab behind the es_ rows.
+        posterior: None, or a utils.fit_monitor.GroupedPosteriorMonitor: the sample mean and m2 of every instance's outputs after
+        a burn-in (with imgs_gt: the PSNR of that mean too), inside the launch list behind the early_stop= launches and in front
+        of ssim= and Adam; independent of the group kind.  Its rows join the slab behind everything else, the sgld and the lr /
+        reg_std rows included; posterior.pooled() pools the B chains (dip_posterior_pool)."""
         B = len(nets)
         if B < 1 or len(net_inputs) != B or len(targets) != B or (masks is not None and len(masks) != B):
             raise ValueError("GroupedFits: one net, one input, one target (and one mask) per instance")
         self.monitor = self._check_monitor(monitor, downsamplers, exp_weight, ema_init, targets, masks)
         self.early_stop = self._check_monitor_slot(early_stop, "early_stop")
         self.ssim = self._check_ssim(ssim, B, self.monitor, exp_weight)
+        self.posterior = self._check_posterior(posterior, B, targets, downsamplers)
         self.downsamplers = None if downsamplers is None else self._check_downsamplers(downsamplers, B, masks)
         self.tv_weights, self.tv_beta = self._check_tv(tv_weights, tv_beta, B, downsamplers)
         self.weight_decay, self.param_noise_std, self.param_noise_seeds = self._check_sgld(
@@ -303,7 +328,8 @@ class GroupedFits:
             ex, mon = self._row0_extra, self.monitor
             own = (("saved", lambda b: net_inputs[b]), ("target", lambda b: targets[b]), ("mask", lambda b: self._mask4(masks[b])),
                    ("taps", lambda b: self.downsamplers[b]._taps), ("mon_gt", lambda b: mon.imgs_gt[b]),
-                   ("mon_hr", lambda b: mon.imgs_HR[b]), ("ssim_gt", lambda b: self.ssim.imgs_gt[b]))
+                   ("mon_hr", lambda b: mon.imgs_HR[b]), ("ssim_gt", lambda b: self.ssim.imgs_gt[b]),
+                   ("post_gt", lambda b: self.posterior.imgs_gt[b]))
             with torch.no_grad():
                 for b in range(B):
                     if b > 0:
@@ -341,19 +367,25 @@ class GroupedFits:
         return contextlib.nullcontext() if self._dry else torch.cuda.device(self.device)
 
     _SLOTS = (("monitor", "mon_", "_mdesc", "_mon"), ("early_stop", "es_", "_edesc", "_es"),
-              ("ssim", "ssim_", "_sdesc", "_ssim"))
+              ("posterior", "post_", "_pdesc", "_post"), ("ssim", "ssim_", "_sdesc", "_ssim"))
 
     def _monitors(self):
-        """The monitors of this group in launch order -- monitor=, then early_stop=, then ssim=, all in front of Adam -- as
-        (monitor, the prefix of its slab rows' names, the attribute of its descriptor, the attribute of its launches)."""
+        """The monitors of this group in launch order -- monitor=, then early_stop=, then posterior=, then ssim= (the order of a
+        solo NativeIteration), all in front of Adam -- as (monitor, the prefix of its slab rows' names, the attribute of its
+        descriptor, the attribute of its launches).  (The slab order differs in one place: the post_ rows lie behind
+        everything else, _build_row0.)"""
         return [(getattr(self, slot), *rest) for slot, *rest in self._SLOTS if getattr(self, slot) is not None]
 
     @staticmethod
     def _check_monitor_slot(m, slot):
-        """What holds for monitor=, early_stop= and ssim= alike: the types the slot takes, and that a monitor is adopted once."""
+        """What holds for monitor=, early_stop=, posterior= and ssim= alike: the types the slot takes, and that a monitor is
+        adopted once."""
         import utils.fit_monitor as FM
         if m is None:
             return None
+        if slot == "posterior" and not isinstance(m, FM.GroupedPosteriorMonitor):
+            raise TypeError(f"dip-amd: GroupedFits(posterior=) takes a utils.fit_monitor.GroupedPosteriorMonitor or None, got "
+                            f"{type(m).__name__} (a solo PosteriorMonitor owns its buffers: they are no rows of the slab)")
         if slot == "ssim":
             if not isinstance(m, FM.GroupedSSIMMonitor):
                 raise TypeError(f"dip-amd: GroupedFits(ssim=) takes a utils.fit_monitor.GroupedSSIMMonitor or None, got "
@@ -362,7 +394,8 @@ class GroupedFits:
             if not isinstance(m, FM.GroupedEarlyStopMonitor):
                 raise TypeError(f"dip-amd: GroupedFits(early_stop=) takes a utils.fit_monitor.GroupedEarlyStopMonitor or None, got "
                                 f"{type(m).__name__} (a solo EarlyStopMonitor owns its buffers: they are no rows of the slab)")
-        elif not isinstance(m, (FM.GroupedFitMonitor, FM.GroupedSRFitMonitor, FM.GroupedRestorationFitMonitor)):
+        elif slot == "monitor" and not isinstance(m, (FM.GroupedFitMonitor, FM.GroupedSRFitMonitor,
+                                                      FM.GroupedRestorationFitMonitor)):
             raise TypeError(f"dip-amd: GroupedFits(monitor=) takes a utils.fit_monitor.GroupedFitMonitor, a GroupedSRFitMonitor, a "
                             f"GroupedRestorationFitMonitor or None, got {type(m).__name__} (a solo FitMonitor cannot "
                             "checkpoint a slab row)")
@@ -387,6 +420,18 @@ class GroupedFits:
             raise ValueError("dip-amd: GroupedSSIMMonitor(with_avg=True) records the SSIM of the group's smoothed output: it "
                              "needs monitor=GroupedFitMonitor(...), which keeps out_avg")
         return ssim
+
+    @classmethod
+    def _check_posterior(cls, posterior, B, targets, downsamplers):
+        """What can be said about `posterior` before anything is planned or allocated (a super-resolution group's HR shape:
+        _carve_monitor)."""
+        if posterior is None:
+            return None
+        cls._check_monitor_slot(posterior, "posterior")
+        posterior._check_count(B)
+        if downsamplers is None:                        # (the net output is shaped like the target)
+            posterior._check_out(B, tuple(targets[0].shape))
+        return posterior
 
     @classmethod
     def _check_monitor(cls, monitor, downsamplers, exp_weight, ema_init, targets, masks=None):
@@ -678,9 +723,10 @@ class GroupedFits:
         self._with_out_conv = sr
         self._head_fwd, self._head_bwd = fwd(eng, self._head), bwd(eng, self._head, at("gl"))
         for m, prefix, desc, ops in self._monitors():
-            d, launches = self._carve_monitor(slab, m, prefix)
-            setattr(self, desc, d)
-            setattr(self, ops, launches)
+            if prefix != "post_":                           # (the posterior's rows: behind everything else, below)
+                d, launches = self._carve_monitor(slab, m, prefix)
+                setattr(self, desc, d)
+                setattr(self, ops, launches)
         if self.sgld:
             # behind everything else: the DipSgldState and the range table of the 4-D parameters (dip_optim.noise_ranges: what
             # a solo FusedAdam over the net's parameters noises), and the extent a solo FusedAdam group steps
@@ -704,6 +750,9 @@ class GroupedFits:
         if self._std_rows:
             ex["reg_std"] = slab.alloc(1)                       # dip_noise_axpy_dev3 reads it
             ex["reg_std"].fill_(self.std[0])
+        # the posterior's rows, only when the keyword is set and behind everything else, the sweep rows included
+        if self.posterior is not None:
+            self._pdesc, self._post = self._carve_monitor(slab, self.posterior, "post_")
 
     def _monitor_sizes(self, m):
         from utils.fit_monitor import monitor_sizes
@@ -712,7 +761,7 @@ class GroupedFits:
                              n_lr=None if ex.get("y") is None else ex["y"].numel(), n_arena=eng.n_arena)
 
     def _carve_monitor(self, slab, m, prefix):
-        """The buffers of monitor m (monitor= or early_stop=) behind everything instance 0 owns so far: what the solo monitor of
+        """The buffers of monitor m (of any of the four slots) behind everything instance 0 owns so far: what the solo monitor of
         its kind allocates for one fit -- its table, utils.fit_monitor -- as per-instance data of the slab under the names
         prefix + key (None where m has no such buffer); ONE descriptor over them (the outputs = the head's, noisy / img / img_LR
         = the target, mask = the group's, loss = the slab's loss scalar: nothing is rewritten per iteration) and the launches
@@ -721,7 +770,7 @@ class GroupedFits:
         eng, ex = self.eng, self._row0_extra
         if self.downsamplers is not None and prefix == "mon_":
             m._check_hr(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
-        if prefix == "ssim_":
+        if prefix in ("ssim_", "post_"):
             m._check_out(self.B, (1, eng.n_out, eng.Hout, eng.Wout))
         z = self._monitor_sizes(m)
         t = dict(out=ex["out"], out_LR=ex.get("y"), noisy=ex["target"], img=ex["target"], img_LR=ex["target"], mask=ex["mask"],
@@ -818,7 +867,8 @@ class GroupedFits:
             # (super-resolution: monitor.update(out_HR, out_LR, total_loss): the psnr_LR / psnr_HR record)
             # es.update(out): behind the monitor (a fall-back has been applied), in front of Adam -- best_params are the
             # parameters that produced best_out; every instance takes its own decision
-            # ssim.update(out): behind both (the monitor's out_avg is this iteration's)
+            # pm.update(out): the sample is the output of the parameters that are about to be stepped and perturbed
+            # ssim.update(out): behind the monitor (its out_avg is this iteration's)
             for _, _, _, ops in self._monitors():
                 for fn, args, name in getattr(self, ops):
                     N.check(fn(*args, st), name)

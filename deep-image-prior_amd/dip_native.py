@@ -164,6 +164,11 @@ class DipPosteriorDesc(C.Structure):
                 ("n", C.c_int64), ("burn_in", C.c_int32), ("every", C.c_int32)]
 
 
+class DipPosteriorRecDesc(C.Structure):
+    _fields_ = DipPosteriorDesc._fields_ + [("gt", C.c_void_p), ("partial", C.c_void_p), ("records", C.c_void_p),
+                                            ("capacity", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DipSsimDesc(C.Structure):
     _fields_ = [("out", C.c_void_p), ("avg", C.c_void_p), ("gt", C.c_void_p), ("map", C.c_void_p), ("partial", C.c_void_p),
                 ("records", C.c_void_p), ("counter", C.c_void_p), ("capacity", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
@@ -171,6 +176,7 @@ class DipSsimDesc(C.Structure):
 
 
 assert C.sizeof(DipSgldState) == 24 and C.sizeof(DipPosteriorDesc) == 56                 # include/dip_hip.h states both
+assert C.sizeof(DipPosteriorRecDesc) == 88                                               # include/dip_hip.h states it
 assert C.sizeof(DipSsimDesc) == 88                                                       # include/dip_hip.h states it
 assert C.sizeof(DipEarlyStopDesc) == 96 and C.sizeof(DipEarlyStopEmvDesc) == 88          # include/dip_hip.h states both
 
@@ -330,6 +336,9 @@ _SIGS = {
     "dip_adam_sgld_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                          C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dip_posterior_dev": (C.c_int, [C.POINTER(DipPosteriorDesc), C.c_void_p]),
+    "dip_posterior_rec_dev": (C.c_int, [C.POINTER(DipPosteriorRecDesc), C.c_void_p]),
+    "dip_posterior_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dip_ssim_nblk": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dip_ssim_dev": (C.c_int, [C.POINTER(DipSsimDesc), C.c_void_p]),
     "dip_lanczos_down_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -533,7 +533,9 @@ class NativeIteration:
     posterior=PosteriorMonitor(img_like, burn_in, every) is a third keyword, independent of the other two: the sample mean and
     variance of the outputs (utils.fit_monitor) as one more command array, dip_posterior_dev, behind monitor= and early_stop= and
     in front of Adam -- where `pm.update(out)` stands in the eager closure, so a sample is the output of the parameters that are
-    about to be stepped and perturbed.  It does not touch the fit; with posterior=None the plan's key is what it was.
+    about to be stepped and perturbed.  It does not touch the fit; with posterior=None the plan's key is what it was.  With
+    PosteriorMonitor(..., img_gt=) the array holds dip_posterior_rec_dev instead (phase name posterior_rec_dev): the same mean
+    and m2, and one record {iteration, mse_mean, psnr_mean} of the posterior mean against the ground truth per SAMPLE.
 
         opt = FusedAdam(get_params('net', net, net_input), lr=LR, weight_decay=5e-8, noise_std=1e-4, noise_seed=0)
         pm = PosteriorMonitor(img_noisy, burn_in=7000, every=50)

@@ -18,7 +18,8 @@ the host reads the record table when it wants to print.
                            exponential form, no ring.  Columns var, var_min, best_iter, wait, stopped
     PosteriorMonitor       no notebook has it either: the sample mean and variance of the outputs of an SGLD fit (Cheng et al.,
                            "A Bayesian Perspective on the Deep Image Prior"; dip_optim.FusedAdam(noise_std=)) after a burn-in,
-                           dip_posterior_dev.  No record table: mean, variance(), count.  Solo only
+                           dip_posterior_dev: mean, variance(), count.  img_gt=: dip_posterior_rec_dev, one record per SAMPLE;
+                           columns iteration, mse_mean, psnr_mean (the PSNR of the posterior mean)
     SSIMMonitor            nor this: the mean structural similarity of the output against a ground truth (and of a smoothed
                            output, img_avg=), dip_ssim_dev; columns ssim, ssim_sm.  ssim(x, y) is the one-shot function
 
@@ -63,6 +64,8 @@ every instance takes its own decisions:
     mon = GroupedSRFitMonitor(imgs_HR, capacity=num_iter)                           # GroupedFits(..., downsamplers=downs)
     mon = GroupedRestorationFitMonitor(show_every=50, capacity=num_iter)            # GroupedFits(..., masks=masks)
     sm = GroupedSSIMMonitor(imgs_gt, capacity=num_iter)                             # GroupedFits(..., ssim=sm), any group kind
+    pm = GroupedPosteriorMonitor(burn_in, every, imgs_gt=None)                      # GroupedFits(..., posterior=pm), any group kind
+    pm.mean, pm.variance(), pm.count; pm.pooled(chains=None).rhat                   # B chains pooled: dip_posterior_pool
 
 A kind's device buffers are declared ONCE, in its table below (FIT_BUFFERS ...): the solo monitor allocates them, the group
 carves them from its slab and views them, and the plan's key and keep-alive list name them, all from that table.
@@ -130,6 +133,10 @@ POSTERIOR_BUFFERS = (Buf("mean", lambda z: z.n, lambda z: z.img, init="zero"),
                      Buf("m2", lambda z: z.n, lambda z: z.img, init="zero"),
                      Buf("samples", lambda z: 1, lambda z: z.one, _I32, "zero"),          # the descriptor's `count`
                      _COUNTER)
+# (with a ground truth -- img_gt= / imgs_gt= -- three more, behind the four: the PSNR of the posterior mean, one row per SAMPLE)
+POSTERIOR_REC_BUFFERS = POSTERIOR_BUFFERS + (_image("gt", "gt", lambda m: True),
+                                             Buf("partial", lambda z: z.nblk(z.n), dtype=_F64, view=False),
+                                             _records(3))
 _ssim_valid = lambda z: (*z.img[:-2], z.img[-2] - 10, z.img[-1] - 10)         # the valid positions of an 11 x 11 window
 SSIM_BUFFERS = (_image("gt", "gt", lambda m: True),
                 Buf("map", lambda z: int(np.prod(_ssim_valid(z))), _ssim_valid, when=lambda m: m.keep_map),
@@ -176,9 +183,13 @@ def early_stop_emv_descriptor(m, t):
 
 
 def posterior_descriptor(m, t):
-    """DipPosteriorDesc of monitor m (burn_in, every): mean, m2, the sample count and the iteration counter."""
+    """DipPosteriorDesc of monitor m (burn_in, every): mean, m2, the sample count and the iteration counter; with a ground truth
+    DipPosteriorRecDesc: the same and gt, the fp64 partials and the record table of `capacity` sample rows."""
     p = lambda k: _ptr(t.get(k))
-    return N.DipPosteriorDesc(p("out"), p("mean"), p("m2"), p("samples"), p("counter"), t["out"].numel(), m.burn_in, m.every)
+    head = (p("out"), p("mean"), p("m2"), p("samples"), p("counter"), t["out"].numel(), m.burn_in, m.every)
+    if not m.with_gt:
+        return N.DipPosteriorDesc(*head)
+    return N.DipPosteriorRecDesc(*head, p("gt"), p("partial"), p("records"), m.capacity, 0)
 
 
 SSIM_WIN, SSIM_K1, SSIM_K2 = 11, 0.01, 0.03
@@ -196,7 +207,8 @@ def ssim_descriptor(m, t):
 
 _ENTRY = {N.DipFitMonitorDesc: "fit_monitor_dev", N.DipSRMonitorDesc: "sr_monitor_dev",
           N.DipRestoreMonitorDesc: "restore_monitor_dev", N.DipEarlyStopDesc: "early_stop_dev",
-          N.DipEarlyStopEmvDesc: "early_stop_emv_dev", N.DipPosteriorDesc: "posterior_dev", N.DipSsimDesc: "ssim_dev"}
+          N.DipEarlyStopEmvDesc: "early_stop_emv_dev", N.DipPosteriorDesc: "posterior_dev",
+          N.DipPosteriorRecDesc: "posterior_rec_dev", N.DipSsimDesc: "ssim_dev"}
 
 
 def monitor_launches(lib, desc, params_ptr=None, n_arena=0, arena_ptr=None):
@@ -312,8 +324,56 @@ class _EarlyStopKind:
 
 class _PosteriorKind:
     COLUMNS = ()                                                    # no record table: mean, m2 and the sample count
+    REC_COLUMNS = ("iteration", "mse_mean", "psnr_mean")            # with a ground truth: one row per SAMPLE
     BUFFERS, ARENA, _descriptor = POSTERIOR_BUFFERS, None, posterior_descriptor
     head_kind = None
+    with_gt = False
+    MAX_SAMPLES = 2 ** 24
+    MAX_ITER = 2 ** 31 - 1                                          # the int32 iteration index
+
+    def _init_posterior(self, burn_in, every, with_gt, capacity):
+        """(what needs no GPU: the settings) -> the capacity of _init_count: the record rows with a ground truth, else the
+        iteration index's range.  A monitor with a ground truth takes the longer table and the columns as its own."""
+        who = type(self).__name__
+        if int(burn_in) < 0:
+            raise ValueError(f"dip-amd: {who}: burn_in must be >= 0, got {burn_in}")
+        if int(every) < 1:
+            raise ValueError(f"dip-amd: {who}: every must be >= 1, got {every}")
+        if with_gt and not 1 <= int(capacity) <= self.MAX_SAMPLES:
+            raise ValueError(f"dip-amd: {who}: capacity (sample rows of the record table) must be in [1, 2**24], got {capacity}")
+        self.burn_in, self.every, self.with_gt = int(burn_in), int(every), bool(with_gt)
+        if self.with_gt:
+            self.BUFFERS, self.COLUMNS = POSTERIOR_REC_BUFFERS, self.REC_COLUMNS
+        return int(capacity) if self.with_gt else self.MAX_ITER
+
+    def samples_after(self, i):
+        """How many of the iterations [0, i) are samples."""
+        return 0 if i <= self.burn_in else (i - self.burn_in - 1) // self.every + 1
+
+    def _check_room(self, n):
+        """Refuses n more iterations when they would pass the sample cap (or the int32 index), or the record table of a monitor
+        with a ground truth: before anything is issued."""
+        who, k = type(self).__name__, self.samples_after(self.i + int(n))
+        if k > self.MAX_SAMPLES or self.i + int(n) > self.MAX_ITER:
+            raise RuntimeError(f"dip-amd: {who}: {int(n)} more iteration(s) after {self.i} would pass the cap of "
+                               f"2**24 samples (burn_in {self.burn_in}, every {self.every}); sample less often")
+        if self.with_gt and k > self.capacity:
+            raise RuntimeError(f"dip-amd: {who} capacity exceeded ({int(n)} more iteration(s) after {self.i} make {k} samples > "
+                               f"capacity {self.capacity}); construct it with capacity >= the number of samples")
+
+    def history(self):
+        """The records of the samples so far as a [count, 3] float32 numpy array (a grouped monitor: [B, count, 3]): iteration,
+        mse_mean, psnr_mean of the posterior mean against the ground truth; one device->host copy, synchronises once."""
+        return self._table()[..., :self.samples_after(self.i), :].contiguous().cpu().numpy()
+
+    def last(self):
+        """The latest sample's record as a dict keyed by COLUMNS (a grouped monitor: a list of B dicts); synchronises."""
+        k = self.samples_after(self.i)
+        if k < 1:
+            raise RuntimeError(f"dip-amd: {type(self).__name__}.last(): no sample has been taken yet")
+        r = self._table()[..., k - 1, :].contiguous().cpu().numpy()
+        rows = [dict(zip(self.COLUMNS, (float(x) for x in row))) for row in r.reshape(-1, len(self.COLUMNS))]
+        return rows if r.ndim > 1 else rows[0]
 
 
 class _SSIMKind:
@@ -733,45 +793,44 @@ class PosteriorMonitor(_PosteriorKind, _DeviceRecords):
     Perspective on the Deep Image Prior") on the device: iteration i is a sample iff i >= burn_in and (i - burn_in) % every == 0,
     and a sample updates `mean` and `m2` ([1,C,H,W] fp32, zero before the first) by Welford's rule in individually rounded fp32
     operations (dip_posterior_dev; include/dip_hip.h states them).  `mean` is the posterior-mean estimate, variance() = m2 /
-    (count - 1) the per-pixel uncertainty map.  No record table: history() / last() do not apply.
+    (count - 1) the per-pixel uncertainty map.
 
     `img_like` gives the shape [1,C,H,W] and the device of the output.  update(out) is the eager form -- after backward() and
     before the optimiser's step, so the sample is the output of the parameters that are about to be stepped and perturbed --
     and NativeIteration(posterior=this) issues the same entry point in the same place; the two may alternate.  At most 2**24
-    samples (the count is a float in the update): what would pass it is refused before anything is issued.  Solo only: there
-    is no grouped form yet (the buffers are declared in POSTERIOR_BUFFERS like every other kind's)."""
+    samples (the count is a float in the update): what would pass it is refused before anything is issued.  B chains through
+    one launch list: GroupedPosteriorMonitor.
+
+    img_gt= (optional, shaped like img_like) adds the curve the SGLD paper shows, the PSNR of the posterior mean against the
+    ground truth: dip_posterior_rec_dev takes dip_posterior_dev's place -- mean and m2 are those of a monitor without it, bit
+    for bit -- and on every SAMPLE iteration, and only then, writes row number `count` of a [capacity, 3] table {iteration,
+    mse_mean, psnr_mean}.  history() is [count, 3] from one copy, last() a dict; what would pass `capacity` samples is refused
+    before anything is issued.  Without img_gt there is no table: history() / last() raise."""
     SETTINGS = ("burn_in", "every", "n")
-    MAX_SAMPLES = 2 ** 24
     _recorded = _DeviceRecords._advance            # update() goes through the device-indexed entry point: the counter moves
 
-    def __init__(self, img_like, burn_in, every=1):
+    def __init__(self, img_like, burn_in, every=1, img_gt=None, capacity=16384):
         # (what needs no GPU is refused first: the type, the settings)
         if not isinstance(img_like, torch.Tensor):
             raise TypeError("dip-amd: PosteriorMonitor: img_like is a tensor shaped like the net output ([1,C,H,W])")
-        if int(burn_in) < 0:
-            raise ValueError(f"dip-amd: PosteriorMonitor: burn_in must be >= 0, got {burn_in}")
-        if int(every) < 1:
-            raise ValueError(f"dip-amd: PosteriorMonitor: every must be >= 1, got {every}")
-        self.burn_in, self.every = int(burn_in), int(every)
+        capacity = self._init_posterior(burn_in, every, img_gt is not None, capacity)
+        if img_gt is not None and (not isinstance(img_gt, torch.Tensor) or tuple(img_gt.shape) != tuple(img_like.shape)):
+            raise ValueError(f"dip-amd: PosteriorMonitor: img_gt must be a tensor shaped like img_like {tuple(img_like.shape)}, got "
+                             f"{tuple(getattr(img_gt, 'shape', ()))}")
         if not img_like.is_cuda:
             raise RuntimeError("dip-amd: PosteriorMonitor works on MI355X tensors only (no CPU fallback)")
         self.shape, self.n = tuple(img_like.shape), img_like.numel()
         if self.n < 1:
             raise ValueError("dip-amd: PosteriorMonitor: img_like is empty")
-        self._init_device(img_like.device, 2 ** 31 - 1, self.shape, n=self.n)      # (capacity: the int32 iteration index)
-
-    def samples_after(self, i):
-        """How many of the iterations [0, i) are samples."""
-        return 0 if i <= self.burn_in else (i - self.burn_in - 1) // self.every + 1
-
-    def _check_room(self, n):
-        """Refuses n more iterations when they would pass the sample cap (or the int32 index): before anything is issued."""
-        if self.samples_after(self.i + int(n)) > self.MAX_SAMPLES or self.i + int(n) > self.capacity:
-            raise RuntimeError(f"dip-amd: PosteriorMonitor: {int(n)} more iteration(s) after {self.i} would pass the cap of "
-                               f"2**24 samples (burn_in {self.burn_in}, every {self.every}); sample less often")
+        if self.with_gt:
+            self.gt = img_gt.detach().to(img_like.device).contiguous().float()
+            self.SETTINGS = PosteriorMonitor.SETTINGS + ("capacity",)
+        self._init_device(img_like.device, capacity, self.shape, n=self.n)
 
     def _table(self, need=0):
-        raise RuntimeError("dip-amd: PosteriorMonitor keeps no record table (read mean, variance() and count)")
+        if not self.with_gt:
+            raise RuntimeError("dip-amd: PosteriorMonitor keeps no record table (read mean, variance() and count)")
+        return self.records
 
     @property
     def count(self):
@@ -1049,6 +1108,117 @@ class GroupedEarlyStopMonitor(_EarlyStopKind, _GroupedRecords):
         with torch.no_grad():
             for r in rows:
                 params[r].copy_(self.best_params[r])
+
+
+class PooledPosterior(NamedTuple):
+    """What GroupedPosteriorMonitor.pooled() returns: device tensors, nothing synchronised."""
+    mean: torch.Tensor                  # [1, C, H, W] the mean over the pooled chains' means
+    var: torch.Tensor                   # [1, C, H, W] V = (k - 1) / k W + B / k, the pooled estimate of the posterior variance
+    within: torch.Tensor                # [1, C, H, W] W, the mean within-chain variance
+    rhat: Optional[torch.Tensor]        # [1, C, H, W] sqrt(V / W), NaN where W is not positive; None with rhat_map=False
+    summary: torch.Tensor               # fp64 [3]: mean and max of rhat over the other elements, the number of degenerate ones
+
+
+class GroupedPosteriorMonitor(_PosteriorKind, _GroupedRecords):
+    """PosteriorMonitor for the B fits of a dip_group.GroupedFits(..., posterior=this): settings only, until adopted.  A keyword of
+    its own next to monitor=, early_stop= and ssim=, for all three group kinds (plain, masks=, downsamplers=: the sample is the
+    net output, in a super-resolution group the HR output).  One burn_in / every for all B: the chains run in lockstep.  The
+    group that adopts it places mean, m2, samples and counter in its slab rows, behind everything else a row owns -- the lr /
+    reg_std sweep rows included -- and exposes them here: mean and m2 [B, C, H, W], samples and counter [B] int32.  ONE
+    dip_posterior_dev call inside the group bracket, behind the monitor= and early_stop= launches and in front of ssim= and Adam
+    (the order of a solo NativeIteration), serves all B inside the ONE hipGraph of capture(); instance b's rows are those of its
+    solo NativeIteration(posterior=PosteriorMonitor(...)) fit, bit for bit.  `count` is the host's: samples_after(i), no
+    synchronisation.
+
+    imgs_gt= (one [1,C,H,W] image per instance, shaped like the net output) adds the PSNR of every instance's posterior mean:
+    ONE dip_posterior_rec_dev call instead, with the gt, fp64 partial and record rows in the slab; records [B, capacity, 3],
+    history() [B, count, 3], one row per SAMPLE.
+
+    pooled(): B instances over one image with different param_noise_seeds are B independent chains; their pooled mean, the
+    Gelman-Rubin variance estimate and R-hat come from one pass over the rows (dip_posterior_pool), nothing through the host."""
+
+    def __init__(self, burn_in, every=1, imgs_gt=None, capacity=16384):
+        self.imgs_gt = None if imgs_gt is None else list(imgs_gt)
+        if self.imgs_gt is not None:
+            if not self.imgs_gt or any(not isinstance(t, torch.Tensor) for t in self.imgs_gt):
+                raise ValueError("dip-amd: GroupedPosteriorMonitor: imgs_gt holds one ground truth per instance or is None (all or "
+                                 "none)")
+            if self.imgs_gt[0].dim() != 4 or self.imgs_gt[0].shape[0] != 1:
+                raise ValueError(f"dip-amd: GroupedPosteriorMonitor: imgs_gt must be [1,C,H,W] images, got "
+                                 f"{tuple(self.imgs_gt[0].shape)}")
+            self._check_images(self.imgs_gt, [self.imgs_gt[0].shape] * len(self.imgs_gt), "imgs_gt", "imgs_gt[0]")
+        self._init_group(self._init_posterior(burn_in, every, self.imgs_gt is not None, capacity))
+        self._chains = {}
+
+    def _check_count(self, B):
+        """What can be said about imgs_gt before the net output's size is known (the shapes: _check_out)."""
+        if self.imgs_gt is not None and len(self.imgs_gt) != B:
+            raise ValueError(f"dip-amd: GroupedPosteriorMonitor has {len(self.imgs_gt)} imgs_gt for {B} instances")
+
+    def _check_out(self, B, out_shape):
+        """imgs_gt against the (planned) net output: one [1,C,H,W] image per instance."""
+        self._check_images(self.imgs_gt, [out_shape] * B, "imgs_gt", "the net output")
+
+    def _adopted_group(self, who):
+        g = self.group
+        if self.mean is None or g is None:
+            raise RuntimeError(f"dip-amd: GroupedPosteriorMonitor.{who}: " + ("the GroupedFits that adopted this monitor is gone"
+                               if self._adopted else "this monitor has not been given to a GroupedFits yet"))
+        return g
+
+    def _table(self, need=0):
+        self._adopted_group("history")
+        if not self.with_gt:
+            raise RuntimeError("dip-amd: GroupedPosteriorMonitor keeps no record table without imgs_gt= (read mean, variance() and "
+                               "count)")
+        return self.records
+
+    @property
+    def count(self):
+        """Samples taken by every instance once all issued work has run: samples_after(i), from the host's count of issued
+        iterations (nothing is read, nothing synchronises)."""
+        return self.samples_after(self.i)
+
+    def variance(self):
+        """The sample variance of every instance's outputs per element, m2 / (count - 1), [B, C, H, W]; no synchronisation."""
+        self._adopted_group("variance")
+        k = self.count
+        if k < 2:
+            raise RuntimeError(f"dip-amd: GroupedPosteriorMonitor.variance needs at least two samples, {k} taken so far")
+        return self.m2 / float(k - 1)
+
+    def pooled(self, chains=None, rhat_map=True):
+        """The chains pooled (default: all B; any subset of at least 2, in any order, without duplicates -- the sums walk them in
+        list order): a PooledPosterior of device tensors from ONE dip_posterior_pool launch on the current stream, outside the
+        group bracket, with k = count.  Nothing synchronises.  Meaningful where the pooled instances fit one image."""
+        g = self._adopted_group("pooled")
+        k = self.count
+        if k < 2:
+            raise RuntimeError(f"dip-amd: GroupedPosteriorMonitor.pooled needs at least two samples per chain, {k} taken so far")
+        chains = tuple(range(g.B)) if chains is None else tuple(chains)
+        if any(isinstance(c, bool) or int(c) != c for c in chains):
+            raise ValueError(f"dip-amd: GroupedPosteriorMonitor.pooled: chains are instance indices, got {list(chains)}")
+        chains = tuple(int(c) for c in chains)
+        if len(chains) < 2:
+            raise ValueError(f"dip-amd: GroupedPosteriorMonitor.pooled: pooling needs at least 2 chains, got {list(chains)}")
+        if len(set(chains)) != len(chains):
+            raise ValueError(f"dip-amd: GroupedPosteriorMonitor.pooled: a chain is pooled once, got {list(chains)}")
+        if any(not 0 <= c < g.B for c in chains):
+            raise IndexError(f"dip-amd: GroupedPosteriorMonitor.pooled: chains {list(chains)} of a group of {g.B}")
+        dev, shape, n = self.mean.device, (1, *self.mean.shape[1:]), self.mean[0].numel()
+        lib = N.lib()
+        with torch.cuda.device(dev):
+            idx = self._chains.get(chains)
+            if idx is None:
+                idx = self._chains[chains] = torch.tensor(chains, dtype=_I32, device=dev)
+            new = lambda: torch.empty(shape, dtype=_F32, device=dev)
+            out = PooledPosterior(new(), new(), new(), new() if rhat_map else None, torch.empty(3, dtype=_F64, device=dev))
+            partial = torch.empty(3 * lib.dip_fit_monitor_nblk(n), dtype=_F64, device=dev)
+            N.check(lib.dip_posterior_pool(self.mean.data_ptr(), self.m2.data_ptr(), self.mean.stride(0) * 4, idx.data_ptr(),
+                                           len(chains), k, n, out.mean.data_ptr(), out.var.data_ptr(), out.within.data_ptr(),
+                                           _ptr(out.rhat), partial.data_ptr(), out.summary.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream), "posterior_pool")
+        return out
 
 
 class GroupedSSIMMonitor(_SSIMKind, _GroupedRecords):

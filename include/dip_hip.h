@@ -987,6 +987,52 @@ typedef struct DipPosteriorDesc {
 } DipPosteriorDesc;
 int dip_posterior_dev(const DipPosteriorDesc* d, void* stream);
 
+/* dip_posterior_dev with the PSNR of the posterior mean against a ground truth (the curve of the SGLD paper).  mean and m2 are
+ * dip_posterior_dev's, bit for bit: the same kernel body under a template flag.  On a sample iteration -- and only then -- the
+ * element pass also forms, per block, the fp64 sum of (double(mean') - double(gt))^2 over the just-updated mean (threads in
+ * grid-stride order, then a 256-wide LDS tree in a fixed pairing order), and the one thread behind it adds the
+ * dip_fit_monitor_nblk(n) partials in block order and writes, BEFORE count advances, fp32 row number `count` of records:
+ *   record <- {iteration (= counter[0], exact below 2^24), mse_mean = sum / n, psnr_mean = 10 log10(1 / mse_mean)}
+ * (data range 1, as dip_fit_monitor's psnr_gt; 3 floats per row).  A row outside [0, capacity) is not written (the host refuses
+ * first).  Deterministic, no float atomics, nothing synchronises.  Every pointer is required; n, burn_in, every as above,
+ * capacity >= 1, otherwise -1 before anything is launched.  sizeof(DipPosteriorRecDesc) == 88 (LP64).  Grouped instantiations:
+ * family DIP_FAM_LOSS. */
+typedef struct DipPosteriorRecDesc {
+    const float* out;       /* [n] the network output of this iteration */
+    float* mean;            /* [n] */
+    float* m2;              /* [n] sum of squared deviations */
+    int* count;             /* int32[1]: samples taken = the next record row */
+    int* counter;           /* int32[1]: the iteration index, advanced by the call */
+    int64_t n;
+    int burn_in, every;
+    const float* gt;        /* [n] the ground truth */
+    double* partial;        /* dip_fit_monitor_nblk(n) doubles of scratch */
+    float* records;         /* [capacity][3] */
+    int capacity, reserved;
+} DipPosteriorRecDesc;
+int dip_posterior_rec_dev(const DipPosteriorRecDesc* d, void* stream);
+
+/* Pools C chains of one posterior -- rows of `mean` / `m2` at a fixed byte stride (the slab rows of a grouped fit), each holding
+ * k samples -- into the pooled mean, the Gelman-Rubin variance estimate and R-hat (Gelman & Rubin 1992; BDA3 section 11.4).
+ * Row c lies chains[c] * stride bytes behind mean0 / m20; `chains` is a device int32[nchains] list, walked in list order.  Per
+ * element, every operation individually rounded in fp32 and nothing contracted (divisions and the square root correctly
+ * rounded):
+ *   s = 0;  for c: s = s + mean_c          mu = s / (float)C
+ *   w = 0;  for c: w = w + m2_c            W  = w / (float)(C * (k - 1))
+ *   q = 0;  for c: d = mean_c - mu; q = q + d * d        Bk = q / (float)(C - 1)
+ *   f = (float)(k - 1) / (float)k          V  = f * W + Bk          (two roundings)
+ *   R = sqrt(V / W)
+ * mean <- mu, within <- W, var <- V, rhat <- R (rhat may be NULL: no map).  An element with !(W > 0) is degenerate: its R is
+ * NaN and it is left out of the summary.  summary (fp64[3]) <- {mean of R over the other elements, their max, the number of
+ * degenerate elements}; NaN, NaN, n when every element is degenerate.  The summary comes from per-block fp64 partials (a 256-wide
+ * LDS tree in a fixed pairing order) added by one thread in block order: deterministic, no float atomics.  `partial` is scratch
+ * of 3 * dip_fit_monitor_nblk(n) doubles.  256 threads, grid-stride over dip_fit_monitor_nblk(n) blocks; 16-byte accesses when
+ * mean0, m20, stride and the outputs are all 16-byte aligned, 4-byte accesses otherwise (4-byte alignment is required).  The
+ * caller vouches for the chain indices (rows that exist).  One launch pair outside a group bracket: with a bracket open, NULL
+ * pointers, n outside (0, 2^33], k outside [2, 2^24] or nchains < 2 it returns -1 before anything is launched. */
+int dip_posterior_pool(const float* mean0, const float* m20, long long stride, const int* chains, int nchains, int k, int64_t n,
+                       float* mean, float* var, float* within, float* rhat, double* partial, double* summary, void* stream);
+
 /* Mean structural similarity (SSIM; Wang, Bovik, Sheikh, Simoncelli 2004) of the network output -- and, optionally, of its
  * moving average -- against a ground truth.  What it replaces is a host filter behind an `out.detach().cpu()` per iteration;
  * the reference computes no SSIM.  Per channel of [C][H][W] images x (out, or avg) and y (gt):
